@@ -9,6 +9,13 @@ trajectory-iterations of the WHOLE solve (tog_solve_init until no trajectory is 
 check included) on all GPUs / max-over-ranks wall time. The `--steps` window (every trajectory
 active) is reported beside it as ``window_rate``; ``steps``/``warmup``/``ms_per_step`` describe it.
 
+A plain run does what that line needs and no more: set-up, the warm-up and the timed steps, the whole
+solve of the same trajectories, the result line (its roofline object is arithmetic on the window's HIP
+events and a committed PMC summary, no run of its own). ``--full`` adds the legs that take runs of
+their own: the whole solve on two more disjoint start sets (``solve_rate_sets``) and the CPU baseline
+(the C oracle on the host cores, ``cpu_baseline``). ``--dump-outputs DIR`` writes what the timed
+window left on the device after its last step (``dump_outputs``), for comparing two builds.
+
 Multi-GPU: one process per GPU (torch.distributed.run); trajectories are independent so each rank
 solves its own shard (weak scaling). The only collective is one RCCL all-reduce per step of the
 batch statistics [n_active, Σ cost, max c_max].
@@ -75,7 +82,7 @@ def kernel_bytes(n, m, N, p_stage, p_term, trials, dense_knots=1):
 
 
 def bwd_flops(n, m, N, p_x, p_u, sqrt=True):
-    """Useful fp64 FLOPs of one trajectory's square-root backward pass (per backward launch), counted
+    r"""Useful fp64 FLOPs of one trajectory's square-root backward pass (per backward launch), counted
     from the operation sequence of backward_pass.jl:87-169 (the oracle's): per knot
       Q.x/Q.u += [A B]ᵀs                2n(n+m)
       S·[A B], S upper-triangular        (n+m)·n(n+1)
@@ -238,6 +245,38 @@ def cpu_baseline(pkg, orc, seconds=10.0, threads=None):
             "single_thread": {"value": s1 / d1, "sample": f"1 trajectory, {s1} iLQR steps, {d1:.1f} s"}}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together stay well under 64 MB
+DUMP_SEED = 20260
+
+
+def dump_outputs(dirname, h, abi, rank=0, world=1):
+    """Write the state the timed window's last ``tog_solve_step`` left on the device, as a caller of
+    the step API reads it back (tog_get): X (B, N, n), U (B, N-1, m) and, from the statistics rows,
+    the per-trajectory cost, c_max, iterations (TOG_STAT_TOTAL_STEPS) and status flags (B,), fp64, one
+    ``<name>.npy`` each (``<name>_rank<r>.npy`` for several ranks). The line-search bookkeeping of the
+    rows (dJ, gradient, alpha, z) is left out: dJ is Inf for a trajectory whose inner solver an outer
+    update has just reset, a sentinel and no result to compare. When the whole batch exceeds the budget, a fixed seeded sample of the trajectories is kept (the
+    same rows of every array, ascending; ``traj_index.npy`` lists them), so two runs with the same
+    arguments write the same trajectories."""
+    os.makedirs(dirname, exist_ok=True)
+    St = h.get(abi.FIELD_STATS)
+    arrays = {"X": h.get(abi.FIELD_X), "U": h.get(abi.FIELD_U), "cost": St[:, abi.STAT_J],
+              "c_max": St[:, abi.STAT_C_MAX], "iterations": St[:, abi.STAT_TOTAL_STEPS],
+              "flags": St[:, abi.STAT_FLAGS]}
+    B = arrays["X"].shape[0]
+    per_traj = sum(a[0].nbytes for a in arrays.values()) + 8
+    keep = int(min(B, max(1, DUMP_BUDGET_BYTES // per_traj)))
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, keep, replace=False))
+    arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+    arrays["traj_index"] = idx.astype(np.float64)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), a.astype(np.float64, copy=False))
+    return {"dir": dirname, "trajectories": keep, "of": B, "dtype": "float64",
+            "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -249,12 +288,18 @@ def main():
                     help="single process: split the GPU's batch into this many slices, each on its own stream "
                          "(tog_create_multi over the same device), so one slice's latency-bound line search "
                          "overlaps another's Jacobians")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the whole solve on two more start sets "
+                         "and the CPU baseline (headline workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write X, U and the statistics rows the last step left "
+                         "(DIR/<name>.npy, float64; a fixed seeded sample of the trajectories when large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-solve-leg", action="store_true", help="skip the full-solve timing leg")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--solve-sets", type=int, default=None,
                     help="whole solves on this many disjoint start sets (offsets 0, B, 2B per GPU slice); value is "
-                         "set 0's, the others are reported beside it (default: 3 for the headline, else 1)")
+                         "set 0's, the others are reported beside it (default: 1; with --full, 3 for the headline)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -340,6 +385,7 @@ def main():
     St = h.get(abi.FIELD_STATS)
     trials = float(np.mean(St[:, abi.STAT_LS_TRIALS][St[:, abi.STAT_LS_TRIALS] > 0])) if np.any(
         St[:, abi.STAT_LS_TRIALS] > 0) else 1.0
+    dumped = dump_outputs(args.dump_outputs, h, abi, rank, world) if args.dump_outputs else None
 
     if dist is not None:
         window_rate, steps_all, elapsed = pkg.distributed.job_rate(steps_done, elapsed, dist,
@@ -397,7 +443,8 @@ def main():
     solve_sets = None
     if not args.no_solve_leg:
         solve_leg = time_solve(h, abi, mode, prob, dist, allreduce_stats, barrier_sync, local_rank, pkg)
-        nsets = args.solve_sets if args.solve_sets is not None else (3 if args.workload == "quadrotor" else 1)
+        nsets = args.solve_sets if args.solve_sets is not None else (
+            3 if args.full and args.workload == "quadrotor" else 1)
         if nsets > 1:
             # the whole-solve rate depends on each set's slowest trajectories: disjoint start sets of the same
             # size (set s: the job's trajectories s*B*world .. (s+1)*B*world - 1, this rank's contiguous slice)
@@ -419,7 +466,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and args.workload == "quadrotor":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "quadrotor":
             orc = __graft_entry__.load_oracle()
             cpu = cpu_baseline(pkg, orc, seconds=args.cpu_seconds)
         line = {
@@ -450,6 +497,8 @@ def main():
             "mfma": (measured_mfma(args.workload) if args.workload == "kuka" else None),
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

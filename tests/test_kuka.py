@@ -193,14 +193,14 @@ def test_notebook_solve_log(tog, oracle):
     assert abs(o.max_violation() - log["outer"][-1]["c_max"]) < 1e-8
 
 
-def test_host_model_bitwise_equal_to_oracle(oracle):
+def test_host_model_bitwise_equal_to_oracle(oracle, tmp_path):
     """The HIP model code (csrc/tog_device.hpp Kuka), compiled for the host, reproduces the
     oracle's f, rk3 step and dual Jacobian columns bit for bit."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not pathlib.Path(hipcc).exists():
         pytest.skip("hipcc not available")
     csrc = next(ROOT.glob("*_amd")) / "csrc"
-    exe = pathlib.Path("/tmp") / "tog_kuka_host_check"
+    exe = tmp_path / "tog_kuka_host_check"
     r = subprocess.run([hipcc, "-O1", "-std=c++17", "-ffp-contract=off", "-x", "hip", "--offload-arch=gfx950",
                         "--cuda-host-only", f"-I{csrc}", str(ROOT / "tools" / "kuka_host_check.cpp"), "-o",
                         str(exe), "-ldl"], capture_output=True, text=True)

@@ -16,7 +16,7 @@ if [ "${PART:-suite}" = suite ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
   tail -2 $OUT/smoke.log
 else
-  timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+  timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
   tail -c 600 $OUT/bench.log
   TAG=r5f NO_SQ=1 bash tools/profile_round.sh > $OUT/pr_r5f.log 2>&1 || { tail -20 $OUT/pr_r5f.log; exit 1; }
   timeout -k 10 300 python bench.py --batch 1 --steps 10 --warmup 2 --no-cpu-baseline --no-solve-leg > $OUT/tail_b1.log 2>&1 \

@@ -22,7 +22,7 @@ if [ -n "$TRACE" ]; then
   rm -rf $OUT/trace
   cat $OUT/tail_trace.txt
 fi
-timeout -k 10 400 python bench.py ${BENCH_ARGS:---cpu-seconds 4} > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:---cpu-seconds 4} > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 -c "
 import json;d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 s=d['solve_rate'];print('value',d['value'],'window',d['window_rate'],'ms/step',d['ms_per_step'],'solve',s['wall_s'],s['batch_steps'],s['steps'],s['ms_per_batch_step'],'tail',s['tail'])

@@ -14,7 +14,7 @@ timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 tail -1 $OUT/smoke.log
 timeout -k 10 200 python tools/tail_solve.py --offset 1457 --profile > $OUT/tail_b1.json 2> $OUT/tail_b1.err || { tail $OUT/tail_b1.err; exit 1; }
 cat $OUT/tail_b1.json
-timeout -k 10 400 python bench.py --cpu-seconds 4 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --cpu-seconds 4 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 -c "
 import json;d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 s=d['solve_rate'];print('value',d['value'],'window',d['window_rate'],'ms/step',d['ms_per_step'],'solve',s['wall_s'],s['batch_steps'],s['steps'],s['ms_per_batch_step'])

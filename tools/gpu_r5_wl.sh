@@ -23,7 +23,7 @@ if [ -n "$SQW" ]; then  # one SQ counter pass over a short bench window of workl
   head -8 $OUT/sq_$SQW.txt
 fi
 for w in ${WLS:-quad_maze kuka quadrotor}; do
-  timeout -k 10 400 python bench.py --workload $w --cpu-seconds 4 > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail $OUT/bench_$w.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --workload $w --cpu-seconds 4 > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail $OUT/bench_$w.err; exit 1; }
   python3 -c "
 import json;d=json.loads(open('$OUT/bench_$w.json').read().strip().splitlines()[-1])
 s=d['solve_rate'];print('$w value',d['value'],'window',d['window_rate'],'ms/step',d['ms_per_step'],'solve',s['wall_s'],s['batch_steps'],s['steps'])

@@ -19,7 +19,7 @@ fi
 for spec in $BENCH; do
   wl=${spec%%:*}; args=${spec#*:}; [ "$args" = "$spec" ] && args=""
   args=${args//,/ }
-  timeout -k 10 600 python bench.py --workload $wl --no-cpu-baseline $args > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || { tail $OUT/bench_$wl.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --workload $wl --no-cpu-baseline $args > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || { tail $OUT/bench_$wl.err; exit 1; }
   python3 -c "
 import json;d=json.loads(open('$OUT/bench_$wl.json').read().strip().splitlines()[-1])
 print('$wl', 'value', d['value'], 'window', d['window_rate'], 'ms/step', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])"

@@ -23,7 +23,7 @@ cp gpurun_out/summ_${T}/traffic.json profiles/${T}_traffic.json 2>/dev/null
 cp gpurun_out/summ_${T}q/traffic.json profiles/${T}_quad_maze_traffic.json || exit 1
 cp gpurun_out/summ_${T}k/traffic.json profiles/${T}_kuka_traffic.json || exit 1
 cp gpurun_out/mfma_${T}_kuka.json profiles/${T}_kuka_mfma.json || exit 1
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 for wl in cartpole quad_maze kuka maze_infeasible quadrotor_tv; do
   timeout -k 10 600 python bench.py --workload $wl --no-cpu-baseline > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || { tail $OUT/bench_$wl.err; exit 1; }
 done
