@@ -469,9 +469,11 @@ enum tog_pn_stat {
    when its first trial does not reduce the violation (projected_newton.jl:273-277): such a
    trajectory stops with this flag and keeps the last accepted iterate. */
 #define TOG_TRAJ_PN_ERROR (1 << 11)
-/* The device's projected Newton blocks hold at most 64 rows (n + the rows active at a knot, a row per lane of
-   a wave; the stride is min(n + pmax, 64)): a trajectory whose active set outgrows them stops with
-   TOG_TRAJ_PN_ERROR | TOG_TRAJ_PN_BLOCK and keeps its last iterate. A device limit, not the reference's. */
+/* The device's projected Newton blocks (n + the rows active at a knot) hold 64 rows on the first pass (a row per
+   lane of a wave; the stride is min(n + pmax, 64)). tog_solve_pn solves a trajectory whose active set outgrows
+   them again, from the call's starting point, with wide kernels of 128 rows (a row per thread of two waves), so
+   this flag now means a block above 128 rows: such a trajectory stops with TOG_TRAJ_PN_ERROR | TOG_TRAJ_PN_BLOCK
+   and keeps its last iterate. No built-in model can reach that (n <= 14 and at most 72 rows a knot: 86). */
 #define TOG_TRAJ_PN_BLOCK (1 << 12)
 
 /* solve!(prob, ProjectedNewtonSolver(prob, opts)) (projected_newton.jl:6-20) on every trajectory's

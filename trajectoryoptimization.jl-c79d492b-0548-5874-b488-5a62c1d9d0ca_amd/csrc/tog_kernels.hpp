@@ -3449,8 +3449,11 @@ struct ModelOps {
   void (*update_constraints)(const DevProblem*, const DevBuffers&, long long B, hipStream_t);
   // projected Newton (tog_pn.hpp): phase 0 = k_pn_begin, 1 = k_pn_project, 2 = k_pn_finish, :optimal's
   // 3 = k_pn_kkt, 4 = k_pn_ls_begin, 5 = k_pn_ls_proj, 6 = k_pn_ls_end; null for
-  // the infeasible (slack) models
-  void (*pn)(const DevProblem*, const DevBuffers&, const PNBuffers&, long long B, int integ, int phase, hipStream_t);
+  // the infeasible (slack) models. pn_wide: the same phases with the wide kernels (blocks of 65-128 rows), a
+  // workgroup per slot of W. Both return the hipError_t of raising a kernel's LDS limit (hipSuccess otherwise).
+  int (*pn)(const DevProblem*, const DevBuffers&, const PNBuffers&, long long B, int integ, int phase, hipStream_t);
+  int (*pn_wide)(const DevProblem*, const DevBuffers&, const PNWideBuffers&, long long slots, int integ, int phase,
+                 hipStream_t);
   bool implicit;                   // TOG_RK3_IMPLICIT / TOG_MIDPOINT_IMPLICIT instantiated
   int bwd_lds_bytes;
   int team_tpw;                    // trajectories per wave of k_bwd_team
@@ -3808,38 +3811,50 @@ struct ModelLaunch {
   static void update_constraints(const DevProblem* P, const DevBuffers& Bf, long long B, hipStream_t st) {
     hipLaunchKernelGGL((k_update_constraints<M>), dim3(grid(B, 64)), dim3(64), 0, st, P, Bf);
   }
-  template <int INTEG>
-  static void pn_phase(const DevProblem* P, const DevBuffers& Bf, const PNBuffers& W, long long B, int phase,
-                       hipStream_t st) {
-    // the factoring kernels' LDS is sized by the block stride (pn_lds_bytes; up to 113 KB at SM = 64)
-    const size_t lds = pn_lds_bytes(W.SM, M::n + M::m);
+  // T = WAVE: the narrow kernels over the batch; T = PN_WIDE_THREADS: the wide ones over W's slots
+  template <int INTEG, int T>
+  static hipError_t pn_phase(const DevProblem* P, const DevBuffers& Bf, const PNArg<T>& W, long long B, int phase,
+                             hipStream_t st) {
+    // the factoring kernels' LDS is sized by the block stride (pn_lds_bytes; up to 113 KB at SM = 64; the wide
+    // path's pn_lds_bytes_wide, 130 KB at SM = 128)
+    const size_t lds = T == WAVE ? pn_lds_bytes(W.SM, M::n + M::m) : pn_lds_bytes_wide(W.SM);
+    hipError_t rc = hipSuccess;
     auto big = [&](auto kern) {  // allow dynamic LDS above 64 KB (gfx950: 160 KB per workgroup)
       if (lds > 65536) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipGetLastError();
+        rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (rc != hipSuccess) return;  // reported by the caller; an earlier launch's error stays where it is
       }
-      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), lds, st, P, Bf, W);
+      hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(T), lds, st, P, Bf, W);
     };
     if (phase == 0)
-      hipLaunchKernelGGL((k_pn_begin<M, INTEG>), dim3((unsigned)B), dim3(64), 0, st, P, Bf, W);
+      hipLaunchKernelGGL((k_pn_begin<M, INTEG, T>), dim3((unsigned)B), dim3(T), 0, st, P, Bf, W);
     else if (phase == 1)
-      big(k_pn_project<M, INTEG>);
+      big(k_pn_project<M, INTEG, T>);
     else if (phase == 2)
-      hipLaunchKernelGGL((k_pn_finish<M, INTEG>), dim3((unsigned)B), dim3(64), 0, st, P, Bf, W);
+      hipLaunchKernelGGL((k_pn_finish<M, INTEG, T>), dim3((unsigned)B), dim3(T), 0, st, P, Bf, W);
     else {  // solve_type :optimal
       if (phase == 3)
-        big(k_pn_kkt<M, INTEG>);
+        big(k_pn_kkt<M, INTEG, T>);
       else if (phase == 4)
-        big(k_pn_ls_begin<M, INTEG>);
+        big(k_pn_ls_begin<M, INTEG, T>);
       else if (phase == 5)
-        big(k_pn_ls_proj<M, INTEG>);
+        big(k_pn_ls_proj<M, INTEG, T>);
       else
-        big(k_pn_ls_end<M, INTEG>);
+        big(k_pn_ls_end<M, INTEG, T>);
     }
+    return rc;
   }
-  static void pn(const DevProblem* P, const DevBuffers& Bf, const PNBuffers& W, long long B, int integ, int phase,
-                 hipStream_t st) {
-    with_integ(integ, [&](auto ic) { pn_phase<decltype(ic)::value>(P, Bf, W, B, phase, st); });
+  static int pn(const DevProblem* P, const DevBuffers& Bf, const PNBuffers& W, long long B, int integ, int phase,
+                hipStream_t st) {
+    hipError_t rc = hipSuccess;
+    with_integ(integ, [&](auto ic) { rc = pn_phase<decltype(ic)::value, WAVE>(P, Bf, W, B, phase, st); });
+    return (int)rc;
+  }
+  static int pn_wide(const DevProblem* P, const DevBuffers& Bf, const PNWideBuffers& W, long long slots, int integ,
+                     int phase, hipStream_t st) {
+    hipError_t rc = hipSuccess;
+    with_integ(integ, [&](auto ic) { rc = pn_phase<decltype(ic)::value, PN_WIDE_THREADS>(P, Bf, W, slots, phase, st); });
+    return (int)rc;
   }
   static ModelOps ops() {
     ModelOps o;
@@ -3863,10 +3878,13 @@ struct ModelLaunch {
     o.rollout = rollout;
     o.update_constraints = update_constraints;
     // projected Newton: every model whose [x; u] fits a wave (a lane per variable of a knot)
-    if constexpr (M::n + M::m <= PN_SM_MAX)
+    if constexpr (M::n + M::m <= PN_SM_MAX) {
       o.pn = pn;
-    else
+      o.pn_wide = pn_wide;
+    } else {
       o.pn = nullptr;
+      o.pn_wide = nullptr;
+    }
     o.bwd_lds_bytes = (int)sizeof(BwdLds<M, true>);
     o.team_tpw = TeamCfg<M>::TPW;
     o.team_stride = bwd_team_stride<M>;

@@ -12,7 +12,10 @@
 // blocks are sized by the rows *active* at a knot, not by every row it carries (the quadrotor maze's
 // infeasible problem has 69 rows a knot, of which 13-16 are active), with a stride of
 // SM = min(n + pmax, PN_SM_MAX) rows. A block larger than the stride (more than 64 - n active rows)
-// stops that trajectory with TOG_TRAJ_PN_ERROR | TOG_TRAJ_PN_BLOCK; nothing is written past it.
+// stops that trajectory in this first, narrow pass; nothing is written past it. tog_solve_pn then
+// solves such a trajectory again from its starting point with the wide instantiation of the same
+// kernels (T = 128 threads, still a row per thread, strides up to PN_SM_WIDE_MAX; below), so
+// TOG_TRAJ_PN_ERROR | TOG_TRAJ_PN_BLOCK is left only on a block above 128 rows.
 // The blocks are built in parallel over their entries (a lane per entry), the block Cholesky of
 // S + 1e-2 I sweeps the knots with the current and previous factor staged in LDS (a lane per row
 // for the off-diagonal solves, a lane per entry for the Schur updates), and the substitutions run a
@@ -22,7 +25,18 @@
 
 namespace tog {
 
-constexpr int PN_SM_MAX = 64;  // largest block (n + active rows): a row per lane of the wave
+constexpr int PN_SM_MAX = 64;  // largest block (n + active rows) of the narrow path: a row per lane of the wave
+// The wide path: every kernel below is a template on its workgroup size T. T = WAVE is the narrow path, as
+// it always was. T = PN_WIDE_THREADS (two waves) keeps a row per thread for blocks of up to 128 rows:
+//  - what the narrow path broadcasts or reduces by wave shuffles goes through LDS (pn_xch) and a barrier;
+//  - LDS holds one SM x SM block instead of three (pn_lds<T>): the factor being formed, or the diagonal
+//    factor a substitution uses. The previous factor and the off-diagonal block are read where the narrow
+//    path has already written them, in the workspace (w.Ld, w.Lo); the rows of a block (Yz) alias the block,
+//    since they are live only while S is built or Yᵀ/Y are applied. 130 KB at SM = 128;
+//  - the workspace is sized by the trajectories that need it, a slot a trajectory (PNWideBuffers::slot).
+// Each entry's fma chain is the same chain in one thread, so both paths give the oracle's bits.
+constexpr int PN_SM_WIDE_MAX = 128;
+constexpr int PN_WIDE_THREADS = 128;
 
 struct PNState {
   double viol, c_max, J;
@@ -59,6 +73,20 @@ struct PNBuffers {
   int SM, nb;
   double atol, eps;                 // active_set_tolerance, feasibility_tolerance
 };
+
+// the wide path's workspace: every (B, ...) above is (slots, ...), and workgroup s solves trajectory slot[s]
+struct PNWideBuffers : PNBuffers {
+  const int* slot;
+};
+template <int T>
+using PNArg = std::conditional_t<(T > WAVE), PNWideBuffers, PNBuffers>;
+template <int T>
+__device__ __forceinline__ long long pn_traj(const PNArg<T>& W) {
+  if constexpr (T > WAVE)
+    return W.slot[blockIdx.x];
+  else
+    return blockIdx.x;
+}
 
 // per-trajectory views of the workspace
 struct PNView {
@@ -113,6 +141,26 @@ __device__ __forceinline__ PNView pn_view(const PNBuffers& W, const DevProblem* 
 
 __device__ __forceinline__ void pn_sync() { __syncthreads(); }  // one-wave blocks: orders LDS traffic
 
+// the wide path's exchange slots (two: a pivot loop alternates them, one barrier a pivot)
+__device__ __forceinline__ double* pn_xch() {
+  __shared__ double xch[2];
+  return xch;
+}
+// v of thread 0 to every thread (the narrow path: a wave shuffle)
+template <int T>
+__device__ __forceinline__ double pn_from0(double v, int lane) {
+  if constexpr (T == WAVE) {
+    return __shfl(v, 0, WAVE);
+  } else {
+    double* x = pn_xch();
+    if (lane == 0) x[0] = v;
+    pn_sync();
+    v = x[0];
+    pn_sync();
+    return v;
+  }
+}
+
 // H⁻¹ diagonal (Diagonal(solver.H): Q·dt, R·dt, terminal Qf; cost.jl:214-228). A minimum-time problem's
 // depends on the newton step's X, U (MinTimeCost's hessian!, minimum_time.jl:238-280): k_pn_begin writes it
 // to the view's wt (pn_weights_min_time).
@@ -139,11 +187,11 @@ __device__ __forceinline__ double pn_wu(const DevProblem* P, const PNView& w, in
 // update!'s cost_expansion! of a minimum-time problem (projected_newton.jl:122-148) at X, U, on the diagonal:
 // Q·h² and R·h² for the model's states and controls (dt = h² = u[end]²), R_min_time for τ, 2 ℓ(x, u) +
 // R_min_time for h (ℓ the quadratic stage cost without dt), terminal Qf and R_min_time. A lane per knot.
-template <class M>
+template <class M, int T>
 __device__ void pn_weights_min_time(const DevProblem* P, const PNView& w, const double* X, const double* U, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N;
-  for (int k = lane; k < N; k += WAVE) {
+  for (int k = lane; k < N; k += T) {
     double* wx = w.wt + (size_t)k * n;
     if (k < N - 1) {
       double* wu = w.wt + (size_t)N * n + (size_t)k * m;
@@ -166,14 +214,14 @@ __device__ void pn_weights_min_time(const DevProblem* P, const PNView& w, const 
 
 // dynamics_constraints! + update_constraints! at (X, U): dynamics rows into yd, constraint values
 // into C (projected_newton.jl:36-44,67-73). A lane per knot.
-template <class M, int INTEG>
+template <class M, int INTEG, int T>
 __device__ void pn_eval(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                         const double* U, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, pmax = P->pmax;
   double* C = Bf.C + (size_t)b * N * pmax;
   const double* x0 = Bf.x0 + (size_t)b * n;
-  for (int k = lane; k < N; k += WAVE) {
+  for (int k = lane; k < N; k += T) {
     const double* xk = X + (size_t)k * n;
     if (k == 0)
       for (int i = 0; i < n; i++) w.yd[i] = xk[i] - x0[i];
@@ -191,11 +239,12 @@ __device__ void pn_eval(const DevProblem* P, const DevBuffers& Bf, long long b, 
 
 // active_set! (projected_newton.jl:75-93) and the block sizes. A lane per knot.
 // Returns (to every lane) whether a block outgrew the stride SM; the caller then stops the trajectory.
+template <int T>
 __device__ int pn_active_set(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, double tol,
                              int nb, int lane) {
   const int N = P->N, pmax = P->pmax, n = P->n;
   const double* C = Bf.C + (size_t)b * N * pmax;
-  for (int k = lane; k < N; k += WAVE) {
+  for (int k = lane; k < N; k += T) {
     const ConRow* rows = P->rows + P->knot_off[k];
     int c = 0;
     for (int i = 0; i < P->knot_cnt[k]; i++)
@@ -204,7 +253,7 @@ __device__ int pn_active_set(const DevProblem* P, const DevBuffers& Bf, long lon
   }
   pn_sync();
   int over = 0;
-  for (int bb = lane; bb < nb; bb += WAVE) {
+  for (int bb = lane; bb < nb; bb += T) {
     w.sz[bb] = (bb < N ? n : 0) + (bb >= 1 ? w.na[bb - 1] : 0);
     over |= w.sz[bb] > w.SM;
   }
@@ -212,12 +261,13 @@ __device__ int pn_active_set(const DevProblem* P, const DevBuffers& Bf, long lon
 }
 
 // y[a] into yv (block order) and its Inf norm (NaN propagates); every lane returns it
+template <int T>
 __device__ double pn_gather_y(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, int nb,
                               int lane) {
   const int N = P->N, pmax = P->pmax, n = P->n;
   const double* C = Bf.C + (size_t)b * N * pmax;
   double viol = 0.0;
-  for (int bb = lane; bb < nb; bb += WAVE) {
+  for (int bb = lane; bb < nb; bb += T) {
     double* y = w.V(w.yv, bb);
     int r = 0;
     if (bb < N)
@@ -230,22 +280,29 @@ __device__ double pn_gather_y(const DevProblem* P, const DevBuffers& Bf, long lo
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) viol = tog_jlmax(viol, __shfl_xor(viol, off, WAVE));
+  if constexpr (T > WAVE) {  // the two waves' maxima through LDS
+    static_assert(T == 2 * WAVE, "two exchange slots");
+    double* x = pn_xch();
+    if ((lane & (WAVE - 1)) == 0) x[lane / WAVE] = viol;
+    pn_sync();
+    viol = tog_jlmax(x[0], x[1]);
+  }
   pn_sync();
   return viol;
 }
 
 // rows of block bb on its own variables z_j = (x_j, u_j), j = bb-1, dense into LDS Yz (SM x (n+m))
-template <class M>
+template <class M, int T>
 __device__ void pn_block_rows(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, int bb,
                               const double* X, double* Yz, int lane) {
   constexpr int n = M::n, m = M::m, L = n + m;
   const int N = P->N, pmax = P->pmax, SM = w.SM, j = bb - 1;
-  for (int e = lane; e < SM * L; e += WAVE) Yz[e] = 0.0;
+  for (int e = lane; e < SM * L; e += T) Yz[e] = 0.0;
   pn_sync();
   const int rb = (bb < N) ? n : 0;
   if (bb < N) {
     const double* AB = Bf.AB + ((size_t)b * (N - 1) + j) * n * L;
-    for (int e = lane; e < n * L; e += WAVE) Yz[(e % n) + SM * (e / n)] = AB[e];
+    for (int e = lane; e < n * L; e += T) Yz[(e % n) + SM * (e / n)] = AB[e];
   }
   if (lane < w.na[j]) {
     const ConRow r = P->rows[P->knot_off[j] + w.act[j * pmax + lane]];
@@ -259,21 +316,21 @@ __device__ void pn_block_rows(const DevProblem* P, const DevBuffers& Bf, long lo
 
 // S = Y H⁻¹ Yᵀ by blocks (projected_newton.jl:233-234; structure of _buildShurCompliment!, :728-757);
 // UNIT: Y Yᵀ (multiplier_projection!)
-template <class M, bool UNIT = false>
+template <class M, int T, bool UNIT = false>
 __device__ void pn_build_S(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                            double* Yz, int nb, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, SM = w.SM;
   {
     double* S0 = w.M(w.Sd, 0);
-    for (int e = lane; e < SM * SM; e += WAVE)
+    for (int e = lane; e < SM * SM; e += T)
       S0[e] = ((e % SM) == (e / SM) && (e % SM) < n) ? (UNIT ? 1.0 : pn_wx<M>(P, w, 0, e % SM)) : 0.0;
   }
   for (int bb = 1; bb < nb; bb++) {
     const int j = bb - 1, sb = w.sz[bb], sp = w.sz[bb - 1], nv = (bb < N) ? n + m : n;
-    pn_block_rows<M>(P, Bf, b, w, bb, X, Yz, lane);
+    pn_block_rows<M, T>(P, Bf, b, w, bb, X, Yz, lane);
     double* Sd = w.M(w.Sd, bb);
-    for (int e = lane; e < sb * sb; e += WAVE) {
+    for (int e = lane; e < sb * sb; e += T) {
       const int i = e % sb, l = e / sb;
       double acc = 0.0;
       for (int v = 0; v < nv; v++) {
@@ -285,7 +342,7 @@ __device__ void pn_build_S(const DevProblem* P, const DevBuffers& Bf, long long 
     }
     const double sg = (bb - 1 == 0) ? 1.0 : -1.0;
     double* So = w.M(w.So, bb);
-    for (int e = lane; e < sb * sp; e += WAVE) {
+    for (int e = lane; e < sb * sp; e += T) {
       const int i = e % sb, c = e / sb;
       So[i + SM * c] = (c < n) ? Yz[i + SM * c] * (sg * (UNIT ? 1.0 : pn_wx<M>(P, w, j, c))) : 0.0;
     }
@@ -294,11 +351,16 @@ __device__ void pn_build_S(const DevProblem* P, const DevBuffers& Bf, long long 
 }
 
 // block Cholesky of S + ρI; Lp/Lc: LDS (SM x SM each), LoL: LDS (SM x SM). Returns 0 or a failure.
+template <int T>
 __device__ int pn_factor(const PNView& w, int nb, double rho, double* Lp, double* Lc, double* LoL, int lane) {
   const int SM = w.SM;
   for (int bb = 0; bb < nb; bb++) {
     const int sb = w.sz[bb];
     const int sp = bb >= 1 ? w.sz[bb - 1] : 0;
+    if constexpr (T > WAVE) {  // wide: the previous factor and Lo_b stay in the workspace; LDS holds Lc alone
+      Lp = w.M(w.Ld, bb >= 1 ? bb - 1 : 0);
+      LoL = w.M(w.Lo, bb);
+    }
     if (bb >= 1 && lane < sb) {  // Lo_b = So_b Lp^{-T}: lane i solves Lp y = So_b[i, :]ᵀ
       const double* So = w.M(w.So, bb);
       for (int l = 0; l < sp; l++) {
@@ -309,7 +371,7 @@ __device__ int pn_factor(const PNView& w, int nb, double rho, double* Lp, double
     }
     pn_sync();
     const double* Sd = w.M(w.Sd, bb);
-    for (int e = lane; e < sb * sb; e += WAVE) {
+    for (int e = lane; e < sb * sb; e += T) {
       const int i = e % sb, l = e / sb;
       if (i < l) continue;
       double t = Sd[i + SM * l];
@@ -327,7 +389,7 @@ __device__ int pn_factor(const PNView& w, int nb, double rho, double* Lp, double
       if (lane > j && lane < sb) Lc[lane + SM * j] = Lc[lane + SM * j] / d;
       pn_sync();
       const int t = sb - j - 1;
-      for (int e = lane; e < t * t; e += WAVE) {
+      for (int e = lane; e < t * t; e += T) {
         const int i = j + 1 + e % t, l = j + 1 + e / t;
         if (i >= l) Lc[i + SM * l] = fma(-Lc[i + SM * j], Lc[l + SM * j], Lc[i + SM * l]);
       }
@@ -335,10 +397,12 @@ __device__ int pn_factor(const PNView& w, int nb, double rho, double* Lp, double
     }
     double* Ld = w.M(w.Ld, bb);
     double* Lo = w.M(w.Lo, bb);
-    for (int e = lane; e < SM * SM; e += WAVE) {
+    for (int e = lane; e < SM * SM; e += T) {
       Ld[e] = Lc[e];
-      Lp[e] = Lc[e];
-      if (bb >= 1) Lo[e] = LoL[e];
+      if constexpr (T == WAVE) {
+        Lp[e] = Lc[e];
+        if (bb >= 1) Lo[e] = LoL[e];
+      }
     }
     pn_sync();
   }
@@ -347,6 +411,7 @@ __device__ int pn_factor(const PNView& w, int nb, double rho, double* Lp, double
 
 // x = (S + ρI)⁻¹ r through the block factor (a row per lane, pivots broadcast by __shfl).
 // T1, T2: LDS staging (SM x SM) of the blocks being used; xn: LDS (SM) previous block's solution.
+template <int T>
 __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, double* T1, double* T2, double* xn,
                           int lane) {
   const int SM = w.SM;
@@ -354,10 +419,12 @@ __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, d
     const int sb = w.sz[bb], sp = bb >= 1 ? w.sz[bb - 1] : 0;
     const double* Ld = w.M(w.Ld, bb);
     const double* Lo = w.M(w.Lo, bb);
-    for (int e = lane; e < SM * SM; e += WAVE) {
+    for (int e = lane; e < SM * SM; e += T) {
       T1[e] = Ld[e];
-      if (bb >= 1) T2[e] = Lo[e];
+      if constexpr (T == WAVE)
+        if (bb >= 1) T2[e] = Lo[e];
     }
+    if constexpr (T > WAVE) T2 = const_cast<double*>(Lo);  // wide: Lo_b is read in the workspace
     pn_sync();
     double t = 0.0;
     if (lane < sb) {
@@ -367,7 +434,15 @@ __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, d
     double* wb = w.V(w.wv, bb);
     const double dl = (lane < sb) ? T1[lane + SM * lane] : 1.0;  // this lane's pivot L[i,i]
     for (int l = 0; l < sb; l++) {
-      const double wl = __shfl(t / dl, l, WAVE);
+      double wl;
+      if constexpr (T == WAVE) {
+        wl = __shfl(t / dl, l, WAVE);
+      } else {  // wide: the pivot row's thread posts it (slots alternate, so one barrier a pivot)
+        double* xc = pn_xch();
+        if (lane == l) xc[l & 1] = t / dl;
+        pn_sync();
+        wl = xc[l & 1];
+      }
       if (lane == l) wb[l] = wl;
       if (lane > l && lane < sb) t = fma(-T1[lane + SM * l], wl, t);
     }
@@ -378,10 +453,12 @@ __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, d
   for (int bb = nb - 1; bb >= 0; bb--) {  // backward
     const int sb = w.sz[bb], sn = bb + 1 < nb ? w.sz[bb + 1] : 0;
     const double* Ld = w.M(w.Ld, bb);
-    for (int e = lane; e < SM * SM; e += WAVE) {
+    for (int e = lane; e < SM * SM; e += T) {
       T1[e] = Ld[e];
-      if (bb + 1 < nb) T2[e] = w.M(w.Lo, bb + 1)[e];
+      if constexpr (T == WAVE)
+        if (bb + 1 < nb) T2[e] = w.M(w.Lo, bb + 1)[e];
     }
+    if constexpr (T > WAVE) T2 = w.M(w.Lo, bb + 1 < nb ? bb + 1 : bb);
     pn_sync();
     double t = 0.0;
     if (lane < sb) {
@@ -391,7 +468,15 @@ __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, d
     double* xb = w.V(x, bb);
     const double dl = (lane < sb) ? T1[lane + SM * lane] : 1.0;
     for (int l = sb - 1; l >= 0; l--) {
-      const double xl = __shfl(t / dl, l, WAVE);
+      double xl;
+      if constexpr (T == WAVE) {
+        xl = __shfl(t / dl, l, WAVE);
+      } else {
+        double* xc = pn_xch();
+        if (lane == l) xc[l & 1] = t / dl;
+        pn_sync();
+        xl = xc[l & 1];
+      }
       if (lane == l) xb[l] = xl;
       if (lane < l) t = fma(-T1[l + SM * lane], xl, t);
     }
@@ -402,6 +487,7 @@ __device__ void pn_fsolve(const PNView& w, int nb, const double* r, double* x, d
 }
 
 // r = y - S x (a row per lane); |r|₂ with the oracle's sequential sum (lane 0), returned to all lanes
+template <int T>
 __device__ double pn_residual(const PNView& w, int nb, const double* y, const double* x, double* r, double* rl,
                               int lane) {
   const int SM = w.SM;
@@ -433,7 +519,7 @@ __device__ double pn_residual(const PNView& w, int nb, const double* y, const do
       for (int i = 0; i < sb; i++) ss = fma(rl[i], rl[i], ss);
     pn_sync();
   }
-  return sqrt(__shfl(ss, 0, WAVE));
+  return sqrt(pn_from0<T>(ss, lane));
 }
 
 // LDS of the kernels that factor and solve (dynamic, sized by the stride SM and L = n + m): three SM x SM
@@ -444,25 +530,38 @@ struct PNLds {
 __host__ __device__ constexpr size_t pn_lds_bytes(int SM, int L) {
   return sizeof(double) * ((size_t)3 * SM * SM + (size_t)SM * L + 2 * (size_t)SM);
 }
+// the wide path: one SM x SM block (which Yz aliases: SM > 64 >= L) and the two vectors. 130 KB at SM = 128,
+// whatever L; the previous factor and Lo_b are read in the workspace (pn_factor, pn_fsolve)
+__host__ __device__ constexpr size_t pn_lds_bytes_wide(int SM) {
+  return sizeof(double) * ((size_t)SM * SM + 2 * (size_t)SM);
+}
+template <int T>
 __device__ __forceinline__ PNLds pn_lds(int SM, int L) {
   extern __shared__ double pn_smem[];
   PNLds s;
   s.A = pn_smem;
-  s.Bm = s.A + SM * SM;
-  s.Cm = s.Bm + SM * SM;
-  s.Yz = s.Cm + SM * SM;
-  s.vec = s.Yz + SM * L;
+  if constexpr (T == WAVE) {
+    s.Bm = s.A + SM * SM;
+    s.Cm = s.Bm + SM * SM;
+    s.Yz = s.Cm + SM * SM;
+    s.vec = s.Yz + SM * L;
+  } else {
+    s.Bm = s.Yz = s.A;
+    s.Cm = nullptr;
+    s.vec = s.A + SM * SM;
+  }
   s.vec2 = s.vec + SM;
   return s;
 }
 
 // reg_solve(S, y, Sreg, 1e-8, 25) into xv (projected_newton.jl:286-303)
+template <int T>
 __device__ void pn_reg_solve(const PNView& w, int nb, PNLds& sh, PNState& s, int lane) {
-  pn_fsolve(w, nb, w.yv, w.xv, sh.A, sh.Bm, sh.vec, lane);
+  pn_fsolve<T>(w, nb, w.yv, w.xv, sh.A, sh.Bm, sh.vec, lane);
   for (int cnt = 0; cnt < 25; cnt++) {
-    const double nr = pn_residual(w, nb, w.yv, w.xv, w.rv, sh.vec2, lane);
+    const double nr = pn_residual<T>(w, nb, w.yv, w.xv, w.rv, sh.vec2, lane);
     if (nr < 1e-8) break;
-    pn_fsolve(w, nb, w.rv, w.dv, sh.A, sh.Bm, sh.vec, lane);
+    pn_fsolve<T>(w, nb, w.rv, w.dv, sh.A, sh.Bm, sh.vec, lane);
     for (int bb = 0; bb < nb; bb++)
       if (lane < w.sz[bb]) w.V(w.xv, bb)[lane] = w.V(w.xv, bb)[lane] + w.V(w.dv, bb)[lane];
     pn_sync();
@@ -471,7 +570,7 @@ __device__ void pn_reg_solve(const PNView& w, int nb, PNLds& sh, PNState& s, int
 }
 
 // trial point Z_ = Z + α δZ, δZ = -H⁻¹ Yᵀ δλ, into X̄, Ū (a variable per lane)
-template <class M>
+template <class M, int T>
 __device__ void pn_trial(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, double* Yz,
                          double alpha, int lane) {
   constexpr int n = M::n, m = M::m;
@@ -482,7 +581,7 @@ __device__ void pn_trial(const DevProblem* P, const DevBuffers& Bf, long long b,
   double* Ut = Bf.Ub + (size_t)b * (N - 1) * m;
   for (int j = 0; j < N; j++) {
     const int bb = j + 1, nv = (j < N - 1) ? n + m : n;
-    pn_block_rows<M>(P, Bf, b, w, bb, w.Xs, Yz, lane);  // H⁻¹Yᵀ of _projection_solve!: Jacobians at its start
+    pn_block_rows<M, T>(P, Bf, b, w, bb, w.Xs, Yz, lane);  // H⁻¹Yᵀ of _projection_solve!: Jacobians at its start
     if (lane < nv) {
       const int v = lane;
       double t = 0.0;
@@ -501,23 +600,23 @@ __device__ void pn_trial(const DevProblem* P, const DevBuffers& Bf, long long b,
 }
 
 // newton_step! prologue (update!: active set at V) and projection_solve!'s first viol
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_begin(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_begin(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNState& s = W.st[b];
+  PNState& s = W.st[ws];
   if (s.finished) return;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   const int N = P->N;
   if (W.optimal && s.steps > 0) {  // :optimal: every newton step starts from solver.V, not from the returned V_
-    for (int e = lane; e < N * M::n; e += WAVE) Bf.X[(size_t)b * N * M::n + e] = w.Xv[e];
-    for (int e = lane; e < (N - 1) * M::m; e += WAVE) Bf.U[(size_t)b * (N - 1) * M::m + e] = w.Uv[e];
+    for (int e = lane; e < N * M::n; e += T) Bf.X[(size_t)b * N * M::n + e] = w.Xv[e];
+    for (int e = lane; e < (N - 1) * M::m; e += T) Bf.U[(size_t)b * (N - 1) * M::m + e] = w.Uv[e];
     pn_sync();
   }
   if constexpr (ModelTraits<M>::min_time)
-    pn_weights_min_time<M>(P, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
-  pn_eval<M, INTEG>(P, Bf, b, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
-  if (pn_active_set(P, Bf, b, w, W.atol, W.nb, lane)) {
+    pn_weights_min_time<M, T>(P, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
+  pn_eval<M, INTEG, T>(P, Bf, b, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
+  if (pn_active_set<T>(P, Bf, b, w, W.atol, W.nb, lane)) {
     if (lane == 0) {
       s.active0 = Bf.st[b].active;
       s.error = s.over = 1;
@@ -526,9 +625,9 @@ __global__ void __launch_bounds__(64) k_pn_begin(const DevProblem* __restrict__ 
     }
     return;
   }
-  const double viol = pn_gather_y(P, Bf, b, w, W.nb, lane);
+  const double viol = pn_gather_y<T>(P, Bf, b, w, W.nb, lane);
   if (W.optimal) {  // update!'s Jacobians at V: the first k_jacobian of the projection loop, for every trajectory
-    for (int e = lane; e < N * M::n; e += WAVE) w.Xs[e] = Bf.X[(size_t)b * N * M::n + e];
+    for (int e = lane; e < N * M::n; e += T) w.Xs[e] = Bf.X[(size_t)b * N * M::n + e];
     pn_sync();
   }
   if (lane == 0) {
@@ -550,53 +649,53 @@ __device__ __forceinline__ void pn_stop_over(PNState& s, PNState* dst, TrajState
 }
 
 // one pass of projection_solve!'s loop: _projection_solve! (Jacobians from k_jacobian at X, U)
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_project(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_project(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNLds sh = pn_lds(W.SM, M::n + M::m);
-  PNState s = W.st[b];
+  PNLds sh = pn_lds<T>(W.SM, M::n + M::m);
+  PNState s = W.st[ws];
   if (s.finished || s.error || s.count >= 10 || !(s.viol > W.eps)) {  // while count < 10 && viol > eps
     if (W.optimal && lane == 0 && !s.finished) Bf.st[b].active = 0;     // (:optimal: Jacobians at V are kept)
     return;
   }
   constexpr int n = M::n, m = M::m;
   const int N = P->N, nb = W.nb;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   double* X = Bf.X + (size_t)b * N * n;
   double* U = Bf.U + (size_t)b * (N - 1) * m;
   s.count++;
   s.projections++;
-  for (int e = lane; e < N * n; e += WAVE) w.Xs[e] = X[e];
-  pn_eval<M, INTEG>(P, Bf, b, w, X, U, lane);
-  if (pn_active_set(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[b], Bf.st[b], lane);
-  const double viol0 = pn_gather_y(P, Bf, b, w, nb, lane);
-  pn_build_S<M>(P, Bf, b, w, X, sh.Yz, nb, lane);
+  for (int e = lane; e < N * n; e += T) w.Xs[e] = X[e];
+  pn_eval<M, INTEG, T>(P, Bf, b, w, X, U, lane);
+  if (pn_active_set<T>(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[ws], Bf.st[b], lane);
+  const double viol0 = pn_gather_y<T>(P, Bf, b, w, nb, lane);
+  pn_build_S<M, T>(P, Bf, b, w, X, sh.Yz, nb, lane);
   double viol = viol0;
-  if (pn_factor(w, nb, 1e-2, sh.A, sh.Bm, sh.Cm, lane)) {
+  if (pn_factor<T>(w, nb, 1e-2, sh.A, sh.Bm, sh.Cm, lane)) {
     s.error = 1;  // PosDefException in cholesky
   } else {
     s.has_S = 1;  // solver.stats[:S] = Sreg
     if (W.optimal && lane < nb) {
-      for (int bb = lane; bb < nb; bb += WAVE) w.szS[bb] = w.sz[bb];
+      for (int bb = lane; bb < nb; bb += T) w.szS[bb] = w.sz[bb];
     }
     double viol_prev = viol0;
     for (int count = 0; count < 10; count++) {
       // _projection_linesearch!: y at the current point (last evaluation), δλ, trial, y at the trial
-      const double vls0 = pn_gather_y(P, Bf, b, w, nb, lane);
+      const double vls0 = pn_gather_y<T>(P, Bf, b, w, nb, lane);
       s.linesearches++;
-      pn_reg_solve(w, nb, sh, s, lane);
-      pn_trial<M>(P, Bf, b, w, sh.Yz, 1.0, lane);
+      pn_reg_solve<T>(w, nb, sh, s, lane);
+      pn_trial<M, T>(P, Bf, b, w, sh.Yz, 1.0, lane);
       double* Xt = Bf.Xb + (size_t)b * N * n;
       double* Ut = Bf.Ub + (size_t)b * (N - 1) * m;
-      pn_eval<M, INTEG>(P, Bf, b, w, Xt, Ut, lane);
-      viol = pn_gather_y(P, Bf, b, w, nb, lane);
+      pn_eval<M, INTEG, T>(P, Bf, b, w, Xt, Ut, lane);
+      viol = pn_gather_y<T>(P, Bf, b, w, nb, lane);
       if (!(viol < vls0)) {  // `count += a` (MethodError) in the reference
         s.error = 1;
         break;
       }
-      for (int e = lane; e < N * n; e += WAVE) X[e] = Xt[e];
-      for (int e = lane; e < (N - 1) * m; e += WAVE) U[e] = Ut[e];
+      for (int e = lane; e < N * n; e += T) X[e] = Xt[e];
+      for (int e = lane; e < (N - 1) * m; e += T) U[e] = Ut[e];
       pn_sync();
       const double rate = log10(viol) / log10(viol_prev);
       viol_prev = viol;
@@ -606,24 +705,24 @@ __global__ void __launch_bounds__(64) k_pn_project(const DevProblem* __restrict_
   }
   s.viol = viol;
   if (lane == 0) {
-    W.st[b] = s;
+    W.st[ws] = s;
     if (s.error || s.count >= 10 || !(s.viol > W.eps)) Bf.st[b].active = 0;  // no further Jacobians
   }
 }
 
 // record_iteration!: J = cost(prob), c_max = max_violation(prob) at X, U; the solve! loop's break
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_finish(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_finish(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNState s = W.st[b];
+  PNState s = W.st[ws];
   if (s.finished) return;
   constexpr int n = M::n, m = M::m;
   const int N = P->N, pmax = P->pmax;
   const double* X = Bf.X + (size_t)b * N * n;
   const double* U = Bf.U + (size_t)b * (N - 1) * m;
   double* C = Bf.C + (size_t)b * N * pmax;
-  for (int k = lane; k < N; k += WAVE) {
+  for (int k = lane; k < N; k += T) {
     const int cnt = P->knot_cnt[k];
     const ConRow* rows = P->rows + P->knot_off[k];
     for (int r = 0; r < cnt; r++)
@@ -637,7 +736,7 @@ __global__ void __launch_bounds__(64) k_pn_finish(const DevProblem* __restrict__
   s.J = traj_cost<M>(P, Bf, b, X, U, false, nullptr);
   if (s.error || s.c_max <= W.eps) s.finished = 1;
   if (s.error) Bf.st[b].flags |= TOG_TRAJ_PN_ERROR | (s.over ? TOG_TRAJ_PN_BLOCK : 0);
-  W.st[b] = s;
+  W.st[ws] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -652,12 +751,12 @@ __global__ void __launch_bounds__(64) k_pn_finish(const DevProblem* __restrict__
 // the objective's gradient (cost_expansion!'s gradient!, :139-148) at X, U into w.g; a lane per knot. A
 // minimum-time problem's is MinTimeCost's gradient! (minimum_time.jl:201-237): the padded quadratic cost's at
 // dt = h², R_min_time τ for τ, τ (2 ℓ(x, u) + R_min_time) for h, terminal Qf x + qf and R_min_time τ
-template <class M>
+template <class M, int T>
 __device__ void pn_grad(const DevProblem* P, const PNView& w, const double* X, const double* U, int lane) {
   constexpr int n = M::n, m = M::m;
   constexpr bool MT = ModelTraits<M>::min_time;
   const int N = P->N;
-  for (int k = lane; k < N; k += WAVE) {
+  for (int k = lane; k < N; k += T) {
     const double* x = X + (size_t)k * n;
     double* q = w.g + (size_t)k * (n + m);
     if (k < N - 1) {
@@ -694,10 +793,11 @@ __device__ void pn_grad(const DevProblem* P, const PNView& w, const double* X, c
 }
 
 // duals (full layout) <-> the active duals in block order; a lane per block
+template <int T>
 __device__ void pn_gather_duals(const DevProblem* P, const PNView& w, const double* nu, const double* lc, double* lb,
                                 int nb, int lane) {
   const int N = P->N, pmax = P->pmax, n = P->n;
-  for (int bb = lane; bb < nb; bb += WAVE) {
+  for (int bb = lane; bb < nb; bb += T) {
     double* l = lb + (size_t)bb * w.SM;
     int r = 0;
     if (bb < N)
@@ -707,10 +807,11 @@ __device__ void pn_gather_duals(const DevProblem* P, const PNView& w, const doub
   }
   pn_sync();
 }
+template <int T>
 __device__ void pn_scatter_duals(const DevProblem* P, const PNView& w, const double* lb, double* nu, double* lc,
                                  int nb, int lane) {
   const int N = P->N, pmax = P->pmax, n = P->n;
-  for (int bb = lane; bb < nb; bb += WAVE) {
+  for (int bb = lane; bb < nb; bb += T) {
     const double* l = lb + (size_t)bb * w.SM;
     int r = 0;
     if (bb < N)
@@ -722,14 +823,14 @@ __device__ void pn_scatter_duals(const DevProblem* P, const PNView& w, const dou
 }
 
 // out = Yᵀ l: column z_j gets ±l_j (+I initial condition, -I dynamics of block j), then block j+1's rows
-template <class M>
+template <class M, int T>
 __device__ void pn_yt(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                       const double* l, double* out, double* Yz, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, SM = w.SM;
   for (int j = 0; j < N; j++) {
     const int bb = j + 1, nv = (j < N - 1) ? n + m : n;
-    pn_block_rows<M>(P, Bf, b, w, bb, X, Yz, lane);
+    pn_block_rows<M, T>(P, Bf, b, w, bb, X, Yz, lane);
     if (lane < nv) {
       const int v = lane;
       double t = (v < n) ? ((j == 0) ? l[v] : -l[(size_t)j * SM + v]) : 0.0;
@@ -742,14 +843,14 @@ __device__ void pn_yt(const DevProblem* P, const DevBuffers& Bf, long long b, co
 }
 
 // out = Y z (block order): row i of block bb from its ±I term, then block bb's own variables z_{bb-1}
-template <class M>
+template <class M, int T>
 __device__ void pn_ymul(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                         const double* z, double* out, double* Yz, int nb, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, SM = w.SM;
   for (int bb = 0; bb < nb; bb++) {
     const int j = bb - 1, nv = (j < N - 1) ? n + m : n;
-    if (bb >= 1) pn_block_rows<M>(P, Bf, b, w, bb, X, Yz, lane);
+    if (bb >= 1) pn_block_rows<M, T>(P, Bf, b, w, bb, X, Yz, lane);
     if (lane < w.sz[bb]) {
       const int i = lane;
       double t = (bb < N && i < n) ? ((bb == 0) ? z[i] : -z[(size_t)bb * (n + m) + i]) : 0.0;
@@ -762,6 +863,7 @@ __device__ void pn_ymul(const DevProblem* P, const DevBuffers& Bf, long long b, 
 }
 
 // |[g + Yᵀλ; y]|₂ with rz = g + Yᵀλ formed: the oracle's sequential sum of squares (lane 0)
+template <int T>
 __device__ double pn_res_norm(const DevProblem* P, const PNView& w, int nb, int lane) {
   double ss = 0.0;
   if (lane == 0) {
@@ -777,118 +879,118 @@ __device__ double pn_res_norm(const DevProblem* P, const PNView& w, int nb, int 
         ss = fma(y, y, ss);
       }
   }
-  return sqrt(__shfl(ss, 0, WAVE));
+  return sqrt(pn_from0<T>(ss, lane));
 }
 
 // rz = g + Yᵀλ, λ the active rows of (nu, lc)
-template <class M>
+template <class M, int T>
 __device__ void pn_form_r(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                           const double* nu, const double* lc, double* Yz, int nb, int lane) {
   constexpr int n = M::n, m = M::m;
-  pn_gather_duals(P, w, nu, lc, w.lb, nb, lane);
-  pn_yt<M>(P, Bf, b, w, X, w.lb, w.rz, Yz, lane);
-  for (int e = lane; e < P->N * (n + m); e += WAVE) w.rz[e] = w.g[e] + w.rz[e];
+  pn_gather_duals<T>(P, w, nu, lc, w.lb, nb, lane);
+  pn_yt<M, T>(P, Bf, b, w, X, w.lb, w.rz, Yz, lane);
+  for (int e = lane; e < P->N * (n + m); e += T) w.rz[e] = w.g[e] + w.rz[e];
   pn_sync();
 }
 
 // multiplier_projection! (:407-420): λ += -(Y Yᵀ) \ (Y (g + Yᵀλ)); returns the residual norm after it
-template <class M>
+template <class M, int T>
 __device__ double pn_multiplier_projection(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w,
                                            const double* X, double* nu, double* lc, PNLds& sh, int nb, int lane,
                                            int& err) {
-  pn_form_r<M>(P, Bf, b, w, X, nu, lc, sh.Yz, nb, lane);
-  pn_ymul<M>(P, Bf, b, w, X, w.rz, w.tb, sh.Yz, nb, lane);
-  pn_build_S<M, true>(P, Bf, b, w, X, sh.Yz, nb, lane);
+  pn_form_r<M, T>(P, Bf, b, w, X, nu, lc, sh.Yz, nb, lane);
+  pn_ymul<M, T>(P, Bf, b, w, X, w.rz, w.tb, sh.Yz, nb, lane);
+  pn_build_S<M, T, true>(P, Bf, b, w, X, sh.Yz, nb, lane);
   PNView w2 = w;
   w2.Ld = w.Ld2;
   w2.Lo = w.Lo2;
-  if (pn_factor(w2, nb, 0.0, sh.A, sh.Bm, sh.Cm, lane)) {
+  if (pn_factor<T>(w2, nb, 0.0, sh.A, sh.Bm, sh.Cm, lane)) {
     err = 1;  // Y Yᵀ not positive definite
     return NAN;
   }
-  pn_fsolve(w2, nb, w.tb, w.xv, sh.A, sh.Bm, sh.vec, lane);
+  pn_fsolve<T>(w2, nb, w.tb, w.xv, sh.A, sh.Bm, sh.vec, lane);
   for (int bb = 0; bb < nb; bb++)
     if (lane < w.sz[bb]) w.lb[(size_t)bb * w.SM + lane] = w.lb[(size_t)bb * w.SM + lane] + -w.xv[(size_t)bb * w.SM + lane];
   pn_sync();
-  pn_scatter_duals(P, w, w.lb, nu, lc, nb, lane);
-  pn_form_r<M>(P, Bf, b, w, X, nu, lc, sh.Yz, nb, lane);
-  return pn_res_norm(P, w, nb, lane);
+  pn_scatter_duals<T>(P, w, w.lb, nu, lc, nb, lane);
+  pn_form_r<M, T>(P, Bf, b, w, X, nu, lc, sh.Yz, nb, lane);
+  return pn_res_norm<T>(P, w, nb, lane);
 }
 
 // solveKKT_Shur (:436-452): δλ = L \ (y - Y H⁻¹ r) with stats[:S]'s factor, δz = -H⁻¹ (r + Yᵀδλ)
-template <class M>
+template <class M, int T>
 __device__ void pn_kkt(const DevProblem* P, const DevBuffers& Bf, long long b, const PNView& w, const double* X,
                        PNLds& sh, int nb, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N;
-  for (int e = lane; e < N * (n + m); e += WAVE) {
+  for (int e = lane; e < N * (n + m); e += T) {
     const int j = e / (n + m), v = e % (n + m);
     if (j == N - 1 && v >= n) continue;
     const double wv = v < n ? pn_wx<M>(P, w, j, v) : pn_wu<M>(P, w, j, v - n);
     w.dz[e] = wv * w.rz[e];
   }
   pn_sync();
-  pn_ymul<M>(P, Bf, b, w, X, w.dz, w.tb, sh.Yz, nb, lane);
+  pn_ymul<M, T>(P, Bf, b, w, X, w.dz, w.tb, sh.Yz, nb, lane);
   for (int bb = 0; bb < nb; bb++)
     if (lane < w.sz[bb]) w.tb[(size_t)bb * w.SM + lane] = w.yv[(size_t)bb * w.SM + lane] - w.tb[(size_t)bb * w.SM + lane];
   pn_sync();
-  pn_fsolve(w, nb, w.tb, w.xv, sh.A, sh.Bm, sh.vec, lane);
-  pn_yt<M>(P, Bf, b, w, X, w.xv, w.dz, sh.Yz, lane);
-  for (int e = lane; e < N * (n + m); e += WAVE) {
+  pn_fsolve<T>(w, nb, w.tb, w.xv, sh.A, sh.Bm, sh.vec, lane);
+  pn_yt<M, T>(P, Bf, b, w, X, w.xv, w.dz, sh.Yz, lane);
+  for (int e = lane; e < N * (n + m); e += T) {
     const int j = e / (n + m), v = e % (n + m);
     if (j == N - 1 && v >= n) continue;
     const double wv = v < n ? pn_wx<M>(P, w, j, v) : pn_wu<M>(P, w, j, v - n);
     w.dz[e] = -(wv * (w.rz[e] + w.dz[e]));
   }
-  for (int e = lane; e < N * n; e += WAVE) w.dnu[e] = 0.0;
-  for (int e = lane; e < N * P->pmax; e += WAVE) w.dlc[e] = 0.0;
+  for (int e = lane; e < N * n; e += T) w.dnu[e] = 0.0;
+  for (int e = lane; e < N * P->pmax; e += T) w.dlc[e] = 0.0;
   pn_sync();
-  pn_scatter_duals(P, w, w.xv, w.dnu, w.dlc, nb, lane);
+  pn_scatter_duals<T>(P, w, w.xv, w.dnu, w.dlc, nb, lane);
 }
 
 // V_ = solver.V + α δV into X, U and the trial duals
-template <class M>
+template <class M, int T>
 __device__ void pn_ls_trial(const DevProblem* P, const PNView& w, double* X, double* U, double alpha, int lane) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, pm = P->pmax;
-  for (int e = lane; e < N * n; e += WAVE) X[e] = w.Xv[e] + alpha * w.dz[(size_t)(e / n) * (n + m) + e % n];
-  for (int e = lane; e < (N - 1) * m; e += WAVE) U[e] = w.Uv[e] + alpha * w.dz[(size_t)(e / m) * (n + m) + n + e % m];
-  for (int e = lane; e < N * n; e += WAVE) w.nut[e] = w.nu[e] + alpha * w.dnu[e];
-  for (int e = lane; e < N * pm; e += WAVE) w.lct[e] = w.lc[e] + alpha * w.dlc[e];
+  for (int e = lane; e < N * n; e += T) X[e] = w.Xv[e] + alpha * w.dz[(size_t)(e / n) * (n + m) + e % n];
+  for (int e = lane; e < (N - 1) * m; e += T) U[e] = w.Uv[e] + alpha * w.dz[(size_t)(e / m) * (n + m) + n + e % m];
+  for (int e = lane; e < N * n; e += T) w.nut[e] = w.nu[e] + alpha * w.dnu[e];
+  for (int e = lane; e < N * pm; e += T) w.lct[e] = w.lc[e] + alpha * w.dlc[e];
   pn_sync();
 }
 
 // line_search's failure: return solver.V
-template <class M>
+template <class M, int T>
 __device__ void pn_ls_restore(const DevProblem* P, const PNView& w, double* X, double* U, int lane) {
   const int N = P->N;
-  for (int e = lane; e < N * M::n; e += WAVE) X[e] = w.Xv[e];
-  for (int e = lane; e < (N - 1) * M::m; e += WAVE) U[e] = w.Uv[e];
+  for (int e = lane; e < N * M::n; e += T) X[e] = w.Xv[e];
+  for (int e = lane; e < (N - 1) * M::m; e += T) U[e] = w.Uv[e];
   pn_sync();
 }
 
 // after projection_solve! (k_jacobian left Jacobians at w.Xs in AB): cost_expansion!, multiplier_projection!,
 // solveKKT_Shur at solver.V
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_kkt(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_kkt(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNLds sh = pn_lds(W.SM, M::n + M::m);
-  PNState s = W.st[b];
+  PNLds sh = pn_lds<T>(W.SM, M::n + M::m);
+  PNState s = W.st[ws];
   if (!W.optimal || s.finished || s.error) return;
   const int N = P->N, nb = W.nb;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   // stats[:S] must exist (KeyError) and, when this step did not project, match the active set's blocks
   int mismatch = 0;
   if (s.has_S && s.count == 0)
-    for (int bb = lane; bb < nb; bb += WAVE) mismatch |= (w.szS[bb] != w.sz[bb]);
+    for (int bb = lane; bb < nb; bb += T) mismatch |= (w.szS[bb] != w.sz[bb]);
   mismatch = __syncthreads_or(mismatch);
   int err = (!s.has_S || mismatch) ? 1 : 0;
   if (!err) {
-    pn_grad<M>(P, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
-    pn_multiplier_projection<M>(P, Bf, b, w, w.Xs, w.nu, w.lc, sh, nb, lane, err);
+    pn_grad<M, T>(P, w, Bf.X + (size_t)b * N * M::n, Bf.U + (size_t)b * (N - 1) * M::m, lane);
+    pn_multiplier_projection<M, T>(P, Bf, b, w, w.Xs, w.nu, w.lc, sh, nb, lane, err);
   }
-  if (!err) pn_kkt<M>(P, Bf, b, w, w.Xs, sh, nb, lane);
+  if (!err) pn_kkt<M, T>(P, Bf, b, w, w.Xs, sh, nb, lane);
   if (lane == 0) {
     if (err) {
       s.error = 1;
@@ -896,83 +998,83 @@ __global__ void __launch_bounds__(64) k_pn_kkt(const DevProblem* __restrict__ P,
       s.ls = 1;
       Bf.st[b].active = 1;  // line_search's update!: Jacobians at solver.V
     }
-    W.st[b] = s;
+    W.st[ws] = s;
   }
 }
 
 // line_search (:463-472): update! at solver.V, res0, the first trial V_ = V + δV
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_ls_begin(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_ls_begin(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNLds sh = pn_lds(W.SM, M::n + M::m);
-  PNState s = W.st[b];
+  PNLds sh = pn_lds<T>(W.SM, M::n + M::m);
+  PNState s = W.st[ws];
   if (!W.optimal || s.finished || s.error || s.ls != 1) return;
   const int N = P->N, nb = W.nb;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   double* X = Bf.X + (size_t)b * N * M::n;
   double* U = Bf.U + (size_t)b * (N - 1) * M::m;
-  for (int e = lane; e < N * M::n; e += WAVE) w.Xv[e] = X[e];
-  for (int e = lane; e < (N - 1) * M::m; e += WAVE) w.Uv[e] = U[e];
+  for (int e = lane; e < N * M::n; e += T) w.Xv[e] = X[e];
+  for (int e = lane; e < (N - 1) * M::m; e += T) w.Uv[e] = U[e];
   // update!'s cost_expansion! at solver.V: a minimum-time problem's H for the first trial's projection!
-  if constexpr (ModelTraits<M>::min_time) pn_weights_min_time<M>(P, w, X, U, lane);
-  pn_eval<M, INTEG>(P, Bf, b, w, X, U, lane);
-  if (pn_active_set(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[b], Bf.st[b], lane);
-  pn_gather_y(P, Bf, b, w, nb, lane);
-  pn_grad<M>(P, w, X, U, lane);
-  pn_form_r<M>(P, Bf, b, w, X, w.nu, w.lc, sh.Yz, nb, lane);
-  const double res0 = pn_res_norm(P, w, nb, lane);
-  pn_ls_trial<M>(P, w, X, U, 1.0, lane);
+  if constexpr (ModelTraits<M>::min_time) pn_weights_min_time<M, T>(P, w, X, U, lane);
+  pn_eval<M, INTEG, T>(P, Bf, b, w, X, U, lane);
+  if (pn_active_set<T>(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[ws], Bf.st[b], lane);
+  pn_gather_y<T>(P, Bf, b, w, nb, lane);
+  pn_grad<M, T>(P, w, X, U, lane);
+  pn_form_r<M, T>(P, Bf, b, w, X, w.nu, w.lc, sh.Yz, nb, lane);
+  const double res0 = pn_res_norm<T>(P, w, nb, lane);
+  pn_ls_trial<M, T>(P, w, X, U, 1.0, lane);
   if (lane == 0) {
     s.res0 = res0;
     s.alpha = 1.0;
     s.ls_count = 0;
     s.pcount = 0;
     s.ls = 2;
-    W.st[b] = s;  // k_jacobian stays on: the trial's Jacobians
+    W.st[ws] = s;  // k_jacobian stays on: the trial's Jacobians
   }
 }
 
 // one pass of projection! (:328-357) at the trial (Jacobians from k_jacobian there): stop on viol < eps or
 // after 11 Newton steps, else δZ = -H⁻¹Yᵀ (Y H⁻¹ Yᵀ) \ y
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_ls_proj(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_ls_proj(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNLds sh = pn_lds(W.SM, M::n + M::m);
-  PNState s = W.st[b];
+  PNLds sh = pn_lds<T>(W.SM, M::n + M::m);
+  PNState s = W.st[ws];
   if (!W.optimal || s.finished || s.error || s.ls != 2) return;
   constexpr int n = M::n, m = M::m;
   const int N = P->N, nb = W.nb;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   double* X = Bf.X + (size_t)b * N * n;
   double* U = Bf.U + (size_t)b * (N - 1) * m;
-  pn_eval<M, INTEG>(P, Bf, b, w, X, U, lane);
-  if (pn_active_set(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[b], Bf.st[b], lane);
-  const double viol = pn_gather_y(P, Bf, b, w, nb, lane);
+  pn_eval<M, INTEG, T>(P, Bf, b, w, X, U, lane);
+  if (pn_active_set<T>(P, Bf, b, w, W.atol, nb, lane)) return pn_stop_over(s, &W.st[ws], Bf.st[b], lane);
+  const double viol = pn_gather_y<T>(P, Bf, b, w, nb, lane);
   if (viol < W.eps || s.pcount > 10) {
     if (lane == 0) {
       s.ls = 3;
       Bf.st[b].active = 0;  // AB keeps the Jacobians at the projected trial
-      W.st[b] = s;
+      W.st[ws] = s;
     }
     return;
   }
-  pn_build_S<M>(P, Bf, b, w, X, sh.Yz, nb, lane);
+  pn_build_S<M, T>(P, Bf, b, w, X, sh.Yz, nb, lane);
   PNView w2 = w;
   w2.Ld = w.Ld2;
   w2.Lo = w.Lo2;
-  if (pn_factor(w2, nb, 0.0, sh.A, sh.Bm, sh.Cm, lane)) {
+  if (pn_factor<T>(w2, nb, 0.0, sh.A, sh.Bm, sh.Cm, lane)) {
     if (lane == 0) {  // the trial is rejected (oracle pn_line_search: more active rows than free variables)
       s.ls = 4;
       Bf.st[b].active = 0;
-      W.st[b] = s;
+      W.st[ws] = s;
     }
     return;
   }
-  pn_fsolve(w2, nb, w.yv, w.xv, sh.A, sh.Bm, sh.vec, lane);
-  pn_yt<M>(P, Bf, b, w, X, w.xv, w.rz, sh.Yz, lane);
-  for (int e = lane; e < N * (n + m); e += WAVE) {
+  pn_fsolve<T>(w2, nb, w.yv, w.xv, sh.A, sh.Bm, sh.vec, lane);
+  pn_yt<M, T>(P, Bf, b, w, X, w.xv, w.rz, sh.Yz, lane);
+  for (int e = lane; e < N * (n + m); e += T) {
     const int j = e / (n + m), v = e % (n + m);
     if (j == N - 1 && v >= n) continue;
     const double wv = v < n ? pn_wx<M>(P, w, j, v) : pn_wu<M>(P, w, j, v - n);
@@ -984,31 +1086,31 @@ __global__ void __launch_bounds__(64) k_pn_ls_proj(const DevProblem* __restrict_
   }
   if (lane == 0) {
     s.pcount++;
-    W.st[b] = s;
+    W.st[ws] = s;
   }
 }
 
 // line_search (:478-494) after projection!: cost_expansion! and multiplier_projection! at V_, the test
 // res < (1 - 0.01 α) res0, else α /= 2 and the next trial; after 10 trials solver.V. A trial whose
 // Y H⁻¹ Yᵀ or Y Yᵀ does not factor is rejected (the oracle's pn_line_search).
-template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_pn_ls_end(const DevProblem* __restrict__ P, DevBuffers Bf, PNBuffers W) {
-  const long long b = blockIdx.x;
+template <class M, int INTEG, int T = WAVE>
+__global__ void __launch_bounds__(T) k_pn_ls_end(const DevProblem* __restrict__ P, DevBuffers Bf, PNArg<T> W) {
+  const long long ws = blockIdx.x, b = pn_traj<T>(W);  // workspace slot, trajectory (the same on the narrow path)
   const int lane = threadIdx.x;
-  PNLds sh = pn_lds(W.SM, M::n + M::m);
-  PNState s = W.st[b];
+  PNLds sh = pn_lds<T>(W.SM, M::n + M::m);
+  PNState s = W.st[ws];
   if (!W.optimal || s.finished || s.error || (s.ls != 3 && s.ls != 4)) return;
   const int N = P->N, nb = W.nb;
-  const PNView w = pn_view(W, P, b);
+  const PNView w = pn_view(W, P, ws);
   double* X = Bf.X + (size_t)b * N * M::n;
   double* U = Bf.U + (size_t)b * (N - 1) * M::m;
   int rejected = s.ls == 4;  // projection!'s Y H⁻¹ Yᵀ did not factor
   double res = NAN;
   if (!rejected) {
-    pn_grad<M>(P, w, X, U, lane);
+    pn_grad<M, T>(P, w, X, U, lane);
     // cost_expansion!(prob, solver, V_): a minimum-time problem's H at the trial, the next trial's projection!'s
-    if constexpr (ModelTraits<M>::min_time) pn_weights_min_time<M>(P, w, X, U, lane);
-    res = pn_multiplier_projection<M>(P, Bf, b, w, X, w.nut, w.lct, sh, nb, lane, rejected);
+    if constexpr (ModelTraits<M>::min_time) pn_weights_min_time<M, T>(P, w, X, U, lane);
+    res = pn_multiplier_projection<M, T>(P, Bf, b, w, X, w.nut, w.lct, sh, nb, lane, rejected);
   }
   int next = 0;
   if (!rejected && res < (1.0 - s.alpha * 0.01) * s.res0) {
@@ -1017,10 +1119,10 @@ __global__ void __launch_bounds__(64) k_pn_ls_end(const DevProblem* __restrict__
     s.alpha /= 2.0;
     s.ls_count++;
     if (s.ls_count >= 10) {
-      pn_ls_restore<M>(P, w, X, U, lane);
+      pn_ls_restore<M, T>(P, w, X, U, lane);
       s.ls = 0;
     } else {
-      pn_ls_trial<M>(P, w, X, U, s.alpha, lane);
+      pn_ls_trial<M, T>(P, w, X, U, s.alpha, lane);
       s.pcount = 0;
       s.ls = 2;
       next = 1;
@@ -1028,7 +1130,7 @@ __global__ void __launch_bounds__(64) k_pn_ls_end(const DevProblem* __restrict__
   }
   if (lane == 0) {
     if (next) Bf.st[b].active = 1;
-    W.st[b] = s;
+    W.st[ws] = s;
   }
 }
 

@@ -128,6 +128,10 @@ struct tog_handle {
   // projected Newton workspace, allocated by the first tog_solve_pn (tog_pn.hpp)
   PNBuffers pn = {};
   bool pn_alloc = false, pn_opt_alloc = false;
+  // a problem whose blocks can outgrow the narrow stride (n + pmax > 64): X, U as tog_solve_pn found them, for
+  // the wide pass's restart; each trajectory's wide slot (-1: none) and its parked active flag
+  double *pn_X0 = nullptr, *pn_U0 = nullptr;
+  int *pn_slot_of = nullptr, *pn_park = nullptr;
   // solver_pn.stats histories of the last tog_solve_pn: (2, n_steps, B) [cost, c_max], records per trajectory
   std::vector<double> pn_hist;
   std::vector<int32_t> pn_hist_rec;
@@ -430,6 +434,187 @@ __global__ void k_reset_state(TrajState* st, long long B, double mu0) {
   s.active = 1;
   (void)mu0;
   st[b] = s;
+}
+
+// Projected Newton's wide pass (tog_solve_pn), a workgroup per trajectory. enter: a trajectory with a slot
+// goes back to the X, U the call started from, without the narrow pass's flags; every other one is parked
+// (k_jacobian skips it, so nothing of it moves). leave: the parked ones get their active flag back.
+static __global__ void __launch_bounds__(64) k_pn_wide_gate(TrajState* st, const int* __restrict__ slot_of, int* park,
+                                                            double* X, double* U, const double* __restrict__ X0,
+                                                            const double* __restrict__ U0, long long nx, long long nu,
+                                                            int enter) {
+  const long long b = blockIdx.x;
+  if (slot_of[b] < 0) {
+    if (threadIdx.x == 0) {
+      if (enter) {
+        park[b] = st[b].active;
+        st[b].active = 0;
+      } else {
+        st[b].active = park[b];
+      }
+    }
+  } else if (enter) {
+    for (long long e = threadIdx.x; e < nx; e += 64) X[b * nx + e] = X0[b * nx + e];
+    for (long long e = threadIdx.x; e < nu; e += 64) U[b * nu + e] = U0[b * nu + e];
+    if (threadIdx.x == 0) st[b].flags &= ~(TOG_TRAJ_PN_ERROR | TOG_TRAJ_PN_BLOCK);
+  }
+}
+
+// The host loop of solve!(prob, ProjectedNewtonSolver) over one workspace (tog_solve_pn): `launch(phase)` runs a
+// phase's kernel over the workspace's `cnt` workgroups, workgroup s solving trajectory traj(s). Fills the
+// trajectories' pn_hist rows; `stp` returns the states after the last newton step.
+template <class Launch, class Traj>
+static int32_t pn_pass(tog_handle* h, const tog_pn_options* opts, bool optimal, const PNState* d_st, long long cnt,
+                       std::vector<PNState>& stp, Launch&& launch, Traj&& traj) {
+  const long long B = h->B;
+  int32_t rc;
+  auto run = [&](int phase) -> int32_t {
+    const hipError_t e = (hipError_t)launch(phase);
+    if (e != hipSuccess)
+      return fail(TOG_ERR_DEVICE, std::string("projected Newton: the kernel's LDS limit could not be raised: ") + hipGetErrorString(e));
+    return TOG_OK;
+  };
+  stp.assign(cnt, PNState{});
+  for (int step = 0; step < opts->n_steps; step++) {
+    if ((rc = run(0))) return rc;
+    for (int it = 0; it < 10; it++) {
+      h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
+      if ((rc = run(1))) return rc;
+    }
+    if (optimal) {  // the KKT step and its line search: 10 trials of at most 12 projection! passes
+      if ((rc = run(3))) return rc;
+      h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
+      if ((rc = run(4))) return rc;
+      for (int ls = 0; ls < 10; ls++) {
+        for (int it = 0; it < 12; it++) {
+          h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
+          if ((rc = run(5))) return rc;
+        }
+        if ((rc = run(6))) return rc;
+      }
+    }
+    if ((rc = run(2))) return rc;
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(stp.data(), d_st, sizeof(PNState) * cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    for (long long s = 0; s < cnt; s++)
+      if (stp[s].steps == step + 1) {
+        const size_t b = (size_t)traj(s);
+        h->pn_hist[2 * (b * opts->n_steps + step)] = stp[s].J;
+        h->pn_hist[2 * (b * opts->n_steps + step) + 1] = stp[s].c_max;
+      }
+  }
+  return TOG_OK;
+}
+
+// the device's LDS a workgroup may ask for (gfx950: 160 KB), for the check of a projected Newton path's need
+static int32_t pn_lds_limit(tog_handle* h, size_t* out) {
+  int optin = 0, plain = 0;
+  HIPCHECK(hipDeviceGetAttribute(&plain, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+  // (what a kernel may opt into, where the runtime reports it apart from the plain limit)
+  if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, h->device) != hipSuccess) {
+    (void)hipGetLastError();
+    optin = 0;
+  }
+  *out = (size_t)std::max(optin, plain);
+  return TOG_OK;
+}
+
+// device buffers of one call, released when it returns
+struct ScopedDev {
+  std::vector<void*> p;
+  ~ScopedDev() {
+    for (void* v : p) (void)hipFree(v);
+  }
+  template <class T>
+  hipError_t get(T** out, size_t count) {
+    void* v = nullptr;
+    const hipError_t e = hipMalloc(&v, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
+    if (e == hipSuccess) p.push_back(v);
+    *out = (T*)v;
+    return e;
+  }
+};
+
+// tog_solve_pn's second pass: the trajectories `trajs`, whose blocks outgrew the narrow stride, are solved again
+// from the call's starting point with the wide kernels (tog_pn.hpp) in a workspace of trajs.size() slots. Their
+// pn_hist rows are rewritten; `stw` returns their final states, slot by slot.
+static int32_t pn_solve_wide(tog_handle* h, const tog_pn_options* opts, bool optimal, const std::vector<int>& trajs,
+                             std::vector<PNState>& stw) {
+  const long long B = h->B, S = (long long)trajs.size();
+  if (!h->ops->pn_wide) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");
+  PNWideBuffers W = {};
+  W.SM = std::min(h->n + h->pmax, PN_SM_WIDE_MAX);
+  W.nb = h->N + 1;
+  W.optimal = optimal ? 1 : 0;
+  W.atol = opts->active_set_tolerance;
+  W.eps = opts->feasibility_tolerance;
+  size_t lim = 0;
+  int32_t rc = pn_lds_limit(h, &lim);
+  if (rc) return rc;
+  const size_t lds = pn_lds_bytes_wide(W.SM) + 512;  // (+ the kernels' static LDS: exchange slots, barrier votes; 272 bytes)
+  if (lds > lim)
+    return fail(TOG_ERR_UNSUPPORTED, "projected Newton's wide kernels need " + std::to_string(lds) +
+                                         " bytes of LDS a workgroup; the device offers " + std::to_string(lim));
+  const size_t blk = (size_t)S * W.nb * W.SM * W.SM, vec = (size_t)S * W.nb * W.SM;
+  const size_t pm = (size_t)(h->pmax > 0 ? h->pmax : 1);
+  const size_t nz = (size_t)S * h->N * (h->n + h->m), nx = (size_t)S * h->N * h->n, nc = (size_t)S * h->N * pm;
+  const size_t nu = (size_t)S * (h->N - 1) * h->m, nwt = (size_t)S * ((size_t)h->N * h->n + (size_t)(h->N - 1) * h->m);
+  size_t need = sizeof(double) * (4 * blk + 5 * vec + 2 * nx + (h->ops->min_time ? nwt : 0)) +
+                sizeof(int) * (nc + (size_t)S * h->N + 2 * (size_t)S * W.nb) + sizeof(PNState) * (size_t)S;
+  if (optimal) need += sizeof(double) * (2 * blk + 2 * vec + 3 * nz + 4 * nx + 3 * nc + nu) + sizeof(int) * (size_t)S * W.nb;
+  size_t fr = 0, tot = 0;
+  HIPCHECK(hipMemGetInfo(&fr, &tot));
+  if (need > fr)
+    return fail(TOG_ERR_NOMEM, "projected Newton wide workspace of " + std::to_string(S) + " trajectories (" +
+                                   std::to_string(need >> 20) + " MiB) exceeds free device memory (" + std::to_string(fr >> 20) + " MiB)");
+  ScopedDev mem;
+  int* d_slot = nullptr;
+  hipError_t e = hipSuccess;
+  auto get = [&](auto** p, size_t count) {
+    if (e == hipSuccess) e = mem.get(p, count);
+  };
+  get(&W.Sd, blk), get(&W.So, blk), get(&W.Ld, blk), get(&W.Lo, blk);
+  get(&W.yv, vec), get(&W.xv, vec), get(&W.rv, vec), get(&W.wv, vec), get(&W.dv, vec);
+  get(&W.yd, nx), get(&W.Xs, nx), get(&W.act, nc), get(&W.na, (size_t)S * h->N), get(&W.sz, (size_t)S * W.nb);
+  get(&W.st, (size_t)S), get(&d_slot, (size_t)S);
+  if (h->ops->min_time) get(&W.wt, nwt);
+  if (optimal) {
+    get(&W.Ld2, blk), get(&W.Lo2, blk), get(&W.lb, vec), get(&W.tb, vec), get(&W.g, nz), get(&W.rz, nz), get(&W.dz, nz);
+    get(&W.nu, nx), get(&W.dnu, nx), get(&W.nut, nx), get(&W.Xv, nx), get(&W.lc, nc), get(&W.dlc, nc), get(&W.lct, nc);
+    get(&W.Uv, nu), get(&W.szS, (size_t)S * W.nb);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TOG_ERR_NOMEM, std::string("projected Newton wide workspace: ") + hipGetErrorString(e));
+  }
+  W.slot = d_slot;
+  std::vector<int> slot_of(B, -1);
+  for (long long s = 0; s < S; s++) {
+    slot_of[trajs[s]] = (int)s;
+    for (int step = 0; step < opts->n_steps; step++)
+      h->pn_hist[2 * ((size_t)trajs[s] * opts->n_steps + step)] = h->pn_hist[2 * ((size_t)trajs[s] * opts->n_steps + step) + 1] = NAN;
+  }
+  // (the stream is idle: the narrow pass ended with a synchronize)
+  HIPCHECK(hipMemcpy(d_slot, trajs.data(), sizeof(int) * S, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h->pn_slot_of, slot_of.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemsetAsync(W.st, 0, sizeof(PNState) * S, h->stream));
+  if (optimal) {  // PrimalDual(prob): zero duals
+    HIPCHECK(hipMemsetAsync(W.nu, 0, sizeof(double) * nx, h->stream));
+    HIPCHECK(hipMemsetAsync(W.lc, 0, sizeof(double) * nc, h->stream));
+  }
+  const long long tx = (long long)h->N * h->n, tu = (long long)(h->N - 1) * h->m;
+  hipLaunchKernelGGL(k_pn_wide_gate, dim3((unsigned)B), dim3(64), 0, h->stream, h->buf.st, h->pn_slot_of, h->pn_park,
+                     h->buf.X, h->buf.U, h->pn_X0, h->pn_U0, tx, tu, 1);
+  rc = pn_pass(h, opts, optimal, W.st, S, stw,
+               [&](int phase) { return h->ops->pn_wide(h->dP, h->buf, W, S, h->integ, phase, h->stream); },
+               [&](long long s) { return trajs[s]; });
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_pn_wide_gate, dim3((unsigned)B), dim3(64), 0, h->stream, h->buf.st, h->pn_slot_of, h->pn_park,
+                     h->buf.X, h->buf.U, h->pn_X0, h->pn_U0, tx, tu, 0);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(h->stream));  // the workspace is released on return
+  return TOG_OK;
 }
 
 extern "C" {
@@ -1681,11 +1866,23 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
   const bool optimal = opts->solve_type == 1;
   if (opts->n_steps < 0) return fail(TOG_ERR_ARG, "n_steps must be >= 0");
   if (!h->ops->pn) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");
-  // block stride: n + every row of a knot, capped at a wave's 64 rows; blocks are sized by the *active* rows
-  // (k_pn_* flag TOG_TRAJ_PN_BLOCK on a trajectory whose active set outgrows the stride)
+  // block stride of the first pass: n + every row of a knot, capped at a wave's 64 rows; blocks are sized by the
+  // *active* rows. A trajectory whose active set outgrows that stride stops there (PNState::over) and is solved
+  // again below with the wide kernels (pn_solve_wide: strides up to 128 rows, which no built-in model exceeds),
+  // so every problem whose blocks stay within 64 rows runs what it always ran
   const int SM = std::min(h->n + h->pmax, PN_SM_MAX);
+  const bool may_widen = h->n + h->pmax > PN_SM_MAX;
   if (SM < h->n) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n <= 64");
   HIPCHECK(hipSetDevice(h->device));
+  {
+    size_t lim = 0;
+    const int32_t rl = pn_lds_limit(h, &lim);
+    if (rl) return rl;
+    const size_t lds = pn_lds_bytes(SM, h->n + h->m);
+    if (lds > lim)
+      return fail(TOG_ERR_UNSUPPORTED, "projected Newton's kernels need " + std::to_string(lds) +
+                                           " bytes of LDS a workgroup; the device offers " + std::to_string(lim));
+  }
   PNBuffers& W = h->pn;
   const long long B = h->B;
   if (h->pn_alloc && W.SM != SM) return fail(TOG_ERR_ARG, "projected Newton workspace stride changed");
@@ -1696,8 +1893,9 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
     const size_t pm = (size_t)(h->pmax > 0 ? h->pmax : 1);
     // the whole workspace is sized before any allocation: a batch whose block factors do not fit the
     // device's free memory is refused with TOG_ERR_NOMEM (solve it in slices, tog_create_multi)
-    const size_t need = sizeof(double) * (4 * blk + 5 * vec + 2 * (size_t)B * h->N * h->n) +
-                        sizeof(int) * ((size_t)B * h->N * pm + (size_t)B * h->N + (size_t)B * W.nb) +
+    const size_t nsnapX = may_widen ? (size_t)B * h->N * h->n : 0, nsnapU = may_widen ? (size_t)B * (h->N - 1) * h->m : 0;
+    const size_t need = sizeof(double) * (4 * blk + 5 * vec + 2 * (size_t)B * h->N * h->n + nsnapX + nsnapU) +
+                        sizeof(int) * ((size_t)B * h->N * pm + (size_t)B * h->N + (size_t)B * W.nb + (may_widen ? 2 * (size_t)B : 0)) +
                         sizeof(PNState) * (size_t)B;
     size_t fr = 0, tot = 0;
     HIPCHECK(hipMemGetInfo(&fr, &tot));
@@ -1713,6 +1911,8 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
         (rc = dalloc(h, &W.act, (size_t)B * h->N * (h->pmax > 0 ? h->pmax : 1))) ||
         (rc = dalloc(h, &W.na, (size_t)B * h->N)) || (rc = dalloc(h, &W.sz, (size_t)B * W.nb)) ||
         (rc = dalloc(h, &W.st, (size_t)B)) ||
+        (may_widen && ((rc = dalloc(h, &h->pn_X0, nsnapX)) || (rc = dalloc(h, &h->pn_U0, nsnapU)) ||
+                       (rc = dalloc(h, &h->pn_slot_of, (size_t)B)) || (rc = dalloc(h, &h->pn_park, (size_t)B)))) ||
         (h->ops->min_time && (rc = dalloc(h, &W.wt, (size_t)B * ((size_t)h->N * h->n + (size_t)(h->N - 1) * h->m))))) {
       // partial failure: release what this call allocated, so a retry does not leak it
       for (size_t i = mark; i < h->allocs.size(); i++) (void)hipFree(h->allocs[i]);
@@ -1759,41 +1959,29 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
   // record_iteration! (k_pn_finish); a trajectory records in a step iff its step counter moved
   h->pn_hist.assign((size_t)2 * std::max(opts->n_steps, 0) * B, NAN);
   h->pn_hist_steps = opts->n_steps;
-  std::vector<PNState> stp(B);
-  for (int step = 0; step < opts->n_steps; step++) {
-    h->ops->pn(h->dP, h->buf, W, B, h->integ, 0, h->stream);
-    for (int it = 0; it < 10; it++) {
-      h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
-      h->ops->pn(h->dP, h->buf, W, B, h->integ, 1, h->stream);
-    }
-    if (optimal) {  // the KKT step and its line search: 10 trials of at most 12 projection! passes
-      h->ops->pn(h->dP, h->buf, W, B, h->integ, 3, h->stream);
-      h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
-      h->ops->pn(h->dP, h->buf, W, B, h->integ, 4, h->stream);
-      for (int ls = 0; ls < 10; ls++) {
-        for (int it = 0; it < 12; it++) {
-          h->ops->jacobian(h->dP, h->buf, B, h->N, h->integ, h->stream);
-          h->ops->pn(h->dP, h->buf, W, B, h->integ, 5, h->stream);
-        }
-        h->ops->pn(h->dP, h->buf, W, B, h->integ, 6, h->stream);
-      }
-    }
-    h->ops->pn(h->dP, h->buf, W, B, h->integ, 2, h->stream);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(stp.data(), W.st, sizeof(PNState) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    for (long long b = 0; b < B; b++)
-      if (stp[b].steps == step + 1) {
-        h->pn_hist[2 * ((size_t)b * opts->n_steps + step)] = stp[b].J;
-        h->pn_hist[2 * ((size_t)b * opts->n_steps + step) + 1] = stp[b].c_max;
-      }
+  if (may_widen && opts->n_steps > 0) {  // the wide pass restarts from here (a later newton step may be the one that overflows)
+    HIPCHECK(hipMemcpyAsync(h->pn_X0, h->buf.X, sizeof(double) * (size_t)B * h->N * h->n, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->pn_U0, h->buf.U, sizeof(double) * (size_t)B * (h->N - 1) * h->m, hipMemcpyDeviceToDevice, h->stream));
   }
+  std::vector<PNState> stp, stw;
+  int32_t rc = pn_pass(h, opts, optimal, W.st, B, stp,
+                       [&](int phase) { return h->ops->pn(h->dP, h->buf, W, B, h->integ, phase, h->stream); },
+                       [](long long s) { return s; });
+  if (rc) return rc;
+  // the trajectories the narrow pass stopped on a block above its stride: again, with the wide kernels
+  std::vector<int> wide;
+  if (may_widen && opts->n_steps > 0)
+    for (long long b = 0; b < B; b++)
+      if (stp[b].over) wide.push_back((int)b);
+  if (!wide.empty() && (rc = pn_solve_wide(h, opts, optimal, wide, stw))) return rc;
   h->pn_hist_rec.assign(B, 0);
   for (long long b = 0; b < B && opts->n_steps > 0; b++) h->pn_hist_rec[b] = stp[b].steps;
+  for (size_t s = 0; s < wide.size(); s++) h->pn_hist_rec[wide[s]] = stw[s].steps;
   if (out) {
     std::vector<PNState> st(B);
     HIPCHECK(hipMemcpyAsync(st.data(), W.st, sizeof(PNState) * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
+    for (size_t s = 0; s < wide.size(); s++) st[wide[s]] = stw[s];
     for (long long b = 0; b < B; b++) {
       double* o = out + b * TOG_PN_NSTATS;
       o[TOG_PN_VIOL] = st[b].viol;

@@ -423,8 +423,9 @@ class ProjectedNewtonError(RuntimeError):
 def _raise_pn_errors(flags, solver):
     flags = np.asarray(flags)
     if np.any(flags & abi.TRAJ_PN_BLOCK):
-        raise ProjectedNewtonError("projected Newton: a block of n + active rows exceeded the device's 64 rows "
-                                   "(TOG_TRAJ_PN_BLOCK)", np.flatnonzero(flags & abi.TRAJ_PN_BLOCK), solver)
+        raise ProjectedNewtonError("projected Newton: a block of n + active rows exceeded the 128 rows of the "
+                                   "device's wide kernels (TOG_TRAJ_PN_BLOCK; no built-in model can reach it)",
+                                   np.flatnonzero(flags & abi.TRAJ_PN_BLOCK), solver)
     if np.any(flags & abi.TRAJ_PN_ERROR):
         bad = np.flatnonzero(flags & abi.TRAJ_PN_ERROR)
         raise ProjectedNewtonError("projected Newton: line search did not reduce the violation for trajectories "
