@@ -33,7 +33,9 @@ extern "C" {
 /* 4: iteration histories (tog_history_enable, TOG_FIELD_HIST_*), tog_solve_altro_ex / tog_altro_result,
       tog_altro_options.max_steps (was reserved), tog_get_pn_history, tog_batch_stats_begin / _end,
       tog_problem_desc.stage_costs (time-varying objectives) */
-#define TOG_ABI_VERSION 4
+/* 5: per-trajectory linear cost terms and goals within one batch (tog_set_trajectory_costs,
+      tog_set_trajectory_goals) */
+#define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
 enum tog_status_code {
@@ -160,7 +162,10 @@ typedef struct tog_constraint_set {
 /* Problem{T,Discrete} (src/problem.jl:37-72) with LQR/Quadratic objective
    (src/cost.jl:112-157, src/objective.jl:102-114) and per-knot constraint sets
    (src/constraint_sets.jl:157-206). One problem, B independent trajectories
-   that differ in x0 and the initial controls U0. */
+   that differ in x0 and the initial controls U0 and, once set on the handle, in the
+   linear and constant terms of their cost and in their goal
+   (tog_set_trajectory_costs, tog_set_trajectory_goals). The cost Hessians, the
+   dynamics and every other constraint are the batch's. */
 typedef struct tog_problem_desc {
   int32_t model;      /* tog_model_id                       */
   int32_t integrator; /* tog_integrator                     */
@@ -363,6 +368,24 @@ int32_t tog_synchronize(tog_handle* h);
 /* initial_controls!/set_x0!/initial_states! (src/problem.jl:149-160).
    X may be NULL: then X is set to NaN (empty_state, src/problem.jl:232). Host pointers. */
 int32_t tog_set_state(tog_handle* h, const double* x0, const double* U, const double* X);
+/* Per-trajectory linear cost terms: trajectory b's stage cost is
+     1/2 x'Qx + 1/2 u'Ru + u'Hx + q_b'x + r_b'u + c_b   (Q, R, H the batch's: the descriptor's, or knot k's
+   of its stage_costs table), its terminal cost 1/2 x'Qf x + qf_b'x + cf_b. This is what LQRCost(Q, R, xf_b)
+   gives a batch of goals, or a tracking cost a batch of references.
+   lin: per_knot = 0: (n+m+1, B), [q; r; c] of trajectory b at every stage knot;
+        per_knot = 1: (n+m+1, N-1, B).
+   term: (n+1, B), [qf; cf].
+   Either may be NULL (that part stays shared). Both NULL: back to the shared objective.
+   Host pointers; n, m are the handle's. The tables replace the ones of an earlier call and hold from the
+   next tog_solve_init or step-level call on. On a tog_create_multi handle the arrays are split along the
+   batch axis like x0. TOG_ERR_UNSUPPORTED on a TOG_PROB_INFEASIBLE or TOG_PROB_MIN_TIME handle; while
+   tables are set, tog_solve_pn returns TOG_ERR_UNSUPPORTED. */
+int32_t tog_set_trajectory_costs(tog_handle* h, int32_t per_knot, const double* lin, const double* term);
+/* Per-trajectory goals. xf: (ng, B), the values of the terminal set's TOG_CON_GOAL rows for trajectory b
+   (ng = that constraint's row count, in row order). NULL restores the descriptor's.
+   TOG_ERR_ARG when the problem has no goal constraint; TOG_ERR_UNSUPPORTED when a goal row sits at a stage
+   knot or two terminal goal rows constrain one state, and in the cases named above. */
+int32_t tog_set_trajectory_goals(tog_handle* h, const double* xf);
 /* copy a field host->device / device->host (host pointers, sizes per tog_field) */
 int32_t tog_set(tog_handle* h, int32_t field, const double* in);
 int32_t tog_get(tog_handle* h, int32_t field, double* out);

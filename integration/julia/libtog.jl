@@ -20,7 +20,7 @@ using LinearAlgebra: PosDefException
 const libtog = get(ENV, "TOG_LIB", "libtog.so")
 
 # ------------------------------------------------------------------------ include/tog.h mirrors
-const TOG_ABI_VERSION = Int32(4)    # include/tog.h; checked against tog_version() at first use
+const TOG_ABI_VERSION = Int32(5)    # include/tog.h; checked against tog_version() at first use
 const TOG_OK = Int32(0)
 const TOG_RK3, TOG_RK4, TOG_MIDPOINT, TOG_RK3_IMPLICIT, TOG_MIDPOINT_IMPLICIT = Int32.(0:4)
 const TOG_CON_BOUND, TOG_CON_GOAL, TOG_CON_CIRCLES, TOG_CON_SPHERES, TOG_CON_INFEASIBLE, TOG_CON_USER,
@@ -454,6 +454,40 @@ function solve!(probs::Vector{<:Problem{T}}, s::BatchediLQRSolver{T}) where T
     any(f -> f & TOG_TRAJ_SQRT_PD_FAIL != 0, flags) && throw(PosDefException(0))
     any(f -> f & TOG_TRAJ_COST_INCREASED != 0, flags) && error("Cost increased during Forward Pass")
     return s
+end
+
+"""
+    tog_set_trajectory_costs!(solver, lin, term)
+    tog_set_trajectory_goals!(solver, xf)
+
+Per-trajectory linear cost terms and goals within the solver's batch (include/tog.h, ABI 5). `lin` is
+`(n+m+1, B)` with columns `[q; r; c]`, or `(n+m+1, N-1, B)` with a column per stage knot; `term` is `(n+1, B)`
+with columns `[qf; cf]`; `xf` is `(ng, B)`, the values of the terminal goal constraint's rows. `nothing` keeps
+(or restores) the shared values. The cost Hessians stay the batch's. For a batch of `LQRObjective(Q, R, Qf, xf_b, N)`:
+`lin[:, b] = [-Q*xf_b; zeros(m); 0.5*xf_b'Q*xf_b]`, `term[:, b] = [-Qf*xf_b; 0.5*xf_b'Qf*xf_b]`.
+"""
+function tog_set_trajectory_costs!(s::BatchediLQRSolver, lin::Union{Nothing,Array{Float64}},
+                                   term::Union{Nothing,Matrix{Float64}})
+    n, m, N, B = s.n, s.m, s.N, s.B
+    per_knot = Int32(0)
+    if lin !== nothing
+        if size(lin) == (n + m + 1, N - 1, B)
+            per_knot = Int32(1)
+        elseif size(lin) != (n + m + 1, B)
+            throw(ArgumentError("lin must be (n+m+1, B) or (n+m+1, N-1, B)"))
+        end
+    end
+    term === nothing || size(term) == (n + 1, B) || throw(ArgumentError("term must be (n+1, B)"))
+    togcheck(ccall((:tog_set_trajectory_costs, libtog), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}),
+                   s.handle, per_knot, lin === nothing ? C_NULL : lin, term === nothing ? C_NULL : term))
+    return nothing
+end
+
+function tog_set_trajectory_goals!(s::BatchediLQRSolver, xf::Union{Nothing,Matrix{Float64}})
+    xf === nothing || size(xf, 2) == s.B || throw(ArgumentError("xf must be (ng, B)"))
+    togcheck(ccall((:tog_set_trajectory_goals, libtog), Int32, (Ptr{Cvoid}, Ptr{Float64}),
+                   s.handle, xf === nothing ? C_NULL : xf))
+    return nothing
 end
 
 "reset!(solver) (src/solvers.jl:63-67; iLQRSolver's: ρ = dρ = 0, stats cleared, ilqr_solver.jl:146-154)."

@@ -11,7 +11,7 @@ The directory name is not a Python identifier; ``__graft_entry__.load_package()`
 under the alias ``trajopt_amd``.
 """
 from . import abi
-from .problem import (BoundConstraint, CircleConstraints, Constraints, ConstraintSet, Dynamics, GoalConstraint,
+from .problem import (BatchObjective, LQRObjectiveBatch, BoundConstraint, CircleConstraints, Constraints, ConstraintSet, Dynamics, GoalConstraint,
                       LQRCost, LQRCostTerminal, LQRObjective, Model, Objective, Problem, QuadraticCost,
                       SphereConstraints, circle_constraint, discretize_model, goal_constraint, initial_controls_b,
                       initial_states_b, max_violation, midpoint, midpoint_implicit, rk3, rk3_implicit, rk4, set_x0_b, sphere_constraint, add_slack_controls,
@@ -36,5 +36,5 @@ __all__ = [
     "to_tog_options", "Expansion", "backwardpass_b", "cost", "cost_expansion_b", "update_constraints_b", "forwardpass_b", "jacobian_b", "rollout_b",
     "Problems", "add_slack_controls", "InfeasibleConstraint", "infeasible_constraints", "infeasible_problem",
     "line_trajectory", "ProjectedNewtonSolver", "ProjectedNewtonSolverOptions", "to_tog_pn_options",
-    "GenericCost", "generic_cost", "PosDefException", "ProjectedNewtonError",
+    "GenericCost", "generic_cost", "PosDefException", "ProjectedNewtonError", "BatchObjective", "LQRObjectiveBatch",
 ]

@@ -16,7 +16,7 @@ import numpy as np
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "csrc" / "libtog.so"
 
-TOG_ABI_VERSION = 4
+TOG_ABI_VERSION = 5
 
 # models (include/tog.h tog_model_id)
 MODEL_DOUBLE_INTEGRATOR, MODEL_CARTPOLE, MODEL_QUADROTOR, MODEL_CAR, MODEL_PENDULUM, MODEL_KUKA = range(6)
@@ -273,6 +273,8 @@ def load_library(path: os.PathLike | None = None):
     lib.tog_synchronize.argtypes = [vp]
     lib.tog_set_state.argtypes = [vp, _dp, _dp, _dp]
     lib.tog_set.argtypes = [vp, C.c_int32, _dp]
+    lib.tog_set_trajectory_costs.argtypes = [vp, C.c_int32, _dp, _dp]
+    lib.tog_set_trajectory_goals.argtypes = [vp, _dp]
     lib.tog_get.argtypes = [vp, C.c_int32, _dp]
     lib.tog_get_device_ptr.argtypes = [vp, C.c_int32, C.POINTER(vp)]
     lib.tog_dims.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -327,7 +329,8 @@ def load_library(path: os.PathLike | None = None):
                  "tog_solve_ilqr", "tog_solve_al", "tog_solve_pn", "tog_model_load", "tog_model_dims",
                  "tog_model_free", "tog_generic_cost_load", "tog_generic_cost_dims", "tog_generic_cost_expand", "tog_generic_cost_expand_device",
                  "tog_generic_cost_free", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable",
-                 "tog_get_pn_history", "tog_batch_stats_begin", "tog_batch_stats_end"):
+                 "tog_get_pn_history", "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs",
+                 "tog_set_trajectory_goals"):
         getattr(lib, name).restype = C.c_int32
     if lib.tog_version() != TOG_ABI_VERSION:
         raise RuntimeError("libtog ABI version mismatch")
@@ -347,7 +350,7 @@ EXPORTED_SYMBOLS = (
     "tog_solve_al", "tog_default_pn_options", "tog_solve_pn", "tog_model_load", "tog_model_dims", "tog_model_free",
     "tog_generic_cost_load", "tog_generic_cost_dims", "tog_generic_cost_expand", "tog_generic_cost_expand_device", "tog_generic_cost_free",
     "tog_default_altro_options", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable", "tog_get_pn_history",
-    "tog_batch_stats_begin", "tog_batch_stats_end",
+    "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs", "tog_set_trajectory_goals",
 )
 KERNEL_JACOBIAN, KERNEL_BACKWARD, KERNEL_FORWARD, KERNEL_EXPANSION = 0, 1, 2, 3
 NKERNELS = 4

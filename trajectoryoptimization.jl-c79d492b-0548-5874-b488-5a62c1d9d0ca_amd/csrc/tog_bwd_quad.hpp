@@ -170,7 +170,7 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
 #pragma unroll
       for (int i = 0; i < n; i++) Qx[i] = ek[n + m + m * m + i + n * c];
     } else {  // the stage cost's square-root factor (a time-varying Objective's knot kk)
-      const double* cQ = TV ? cost_at<n, m>(P, kk).cQ : P->cQ;
+      const double* cQ = TV ? cost_at<n, m, false>(P, kk, b).cQ : P->cQ;
 #pragma unroll
       for (int i = 0; i < n; i++) Qx[i] = cQ[i + n * c];
     }
@@ -527,7 +527,7 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
         // ---------------------------------------------------------------- C: Q.ux, tmp1
         double Quxc[m];
         if constexpr (TV) {  // knot k's H dt
-          const double* Hk = cost_at<n, m>(P, k).H;
+          const double* Hk = cost_at<n, m, false>(P, k, b).H;
 #pragma unroll
           for (int i = 0; i < m; i++) Quxc[i] = replay ? Cqr[i] : Hk[i + m * c] * dt;
         } else {

@@ -125,8 +125,8 @@ inline bool team_rows_fit(const int* knot_off, const int* knot_cnt, const ConRow
 // active_set augmented_lagrangian_methods.jl:190-195). cr: this knot's rows in the LDS row cache;
 // x, u: the knot's state/control staged in LDS (u == nullptr at the terminal knot). The ordered
 // lists of rows with a state / control gradient are built with ballots (team-uniform control flow).
-template <class M>
-__device__ __forceinline__ void team_rows(const DevBuffers& Bf, long long b, int k, int N, int pmax, int p,
+template <class M, bool PT>
+__device__ __forceinline__ void team_rows(const DevProblem* P, const DevBuffers& Bf, long long b, int k, int N, int pmax, int p,
                                           const ConRow* cr, const double* x, const double* u, RowInfo* rows,
                                           int* xr, int* ur, int& nx, int& nu, int team, int tl, int TEAM) {
   constexpr int n = M::n;
@@ -139,7 +139,7 @@ __device__ __forceinline__ void team_rows(const DevBuffers& Bf, long long b, int
     const int r = base + tl;
     bool isx = false, isu = false;
     if (r < p) {
-      const ConRow row = cr[r];
+      const ConRow row = traj_row<PT>(P, b, cr[r]);
       const double c = row_value<false>(row, x, u);
       const double l = lam[r];
       const bool a = row_inequality<false>(row) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -418,7 +418,7 @@ __device__ __forceinline__ bool cond_exceeds_team(const double (&R)[m][m], const
 // neighbouring teams (coalesced X, U, λ, μ reads and record writes). Lane c forms column c of Q.xx
 // and Q.uu exactly as the fused expansion of round 2 did (same operations, same order: DESIGN.md §3).
 // ============================================================================================
-template <class M, bool SQRT, bool AL, bool TERM>
+template <class M, bool SQRT, bool AL, bool TERM, bool PT>
 __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffers& Bf, long long b, int k,
                                             double* tlds, int tl, int team) {
   using Cfg = TeamCfg<M>;
@@ -433,7 +433,7 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
   double Qxc[n], Quuc[m], Qu[m], Qxs;
   const double xc = xg[c];
   const int diag_mode = P->diag_cost;
-  const CostView C_ = cost_at<n, m>(P, TERM ? 0 : k);  // stage knot k's cost (a time-varying Objective)
+  const CostView C_ = cost_at<n, m, PT>(P, TERM ? 0 : k, b);  // stage knot k's cost (a time-varying Objective)
   if (!TERM && diag_mode == 2) {
     // diagonal cost with +0.0 off-diagonals (host-checked): the per-lane constants are one
     // diagonal entry each, the rest literal zeros -- the same values the general path loads
@@ -483,7 +483,7 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
 #pragma unroll
       for (int j = 0; j < n; j++) a = fma(P->Qf[c + n * j], xg[j], a);
     }
-    Qxs = a + P->qf[c];
+    Qxs = a + term_at<n, PT>(P, b).qf[c];
 #pragma unroll
     for (int i = 0; i < n; i++) Qxc[i] = SQRT ? P->cQf[i + n * c] : P->Qf[i + n * c];
 #pragma unroll
@@ -504,7 +504,7 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
     if (!TERM && colu) us[tl] = ug[tl];
     team_sync();
     int nx, nu;
-    team_rows<M>(Bf, b, k, N, pmax, p, P->rows + P->knot_off[k], xs, TERM ? nullptr : us, rows, xr, ur, nx, nu,
+    team_rows<M, PT>(P, Bf, b, k, N, pmax, p, P->rows + P->knot_off[k], xs, TERM ? nullptr : us, rows, xr, ur, nx, nu,
                  team, tl, TEAM);
     team_sync();
     if (!SQRT && !TERM && P->qpat_on) {  // (qpat_on implies at most QPK pattern rows per column)
@@ -675,7 +675,8 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
 }
 
 // mode 0: every knot; 1: only the dense ones (the others are on k_expand_u); 2: only the terminal knot
-// (one team per trajectory: no stage knot is dense)
+// (one team per trajectory: no stage knot is dense). ALI: bit 0 the AL expansion, bit 1 the per-trajectory
+// variant (PT: q, r, qf and the goal rows' targets from trajectory b's tables)
 template <class M, int SQRTI, int ALI>
 __global__ void __launch_bounds__(64) k_expand_team(const DevProblem* P, DevBuffers Bf, int mode) {
   using Cfg = TeamCfg<M>;
@@ -688,12 +689,12 @@ __global__ void __launch_bounds__(64) k_expand_team(const DevProblem* P, DevBuff
   const long long b = traj_of_slot(Bf, slot, P->B);
   if (b < 0) return;  // whole teams return together (DPP broadcasts stay within a team)
   if (!Bf.st[b].active || Bf.st[b].ls_pend) return;
-  if (mode == 1 && k < N - 1 && !(ALI && P->knot_nx[k] > 0)) return;
+  if (mode == 1 && k < N - 1 && !((ALI & 1) && P->knot_nx[k] > 0)) return;
   double* tlds = expand_lds + (size_t)team * expand_team_stride<M>(P->pmax);
   if (k == N - 1)
-    team_expand<M, SQRTI != 0, ALI != 0, true>(P, Bf, b, k, tlds, tl, team);
+    team_expand<M, SQRTI != 0, (ALI & 1) != 0, true, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, team);
   else
-    team_expand<M, SQRTI != 0, ALI != 0, false>(P, Bf, b, k, tlds, tl, team);
+    team_expand<M, SQRTI != 0, (ALI & 1) != 0, false, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, team);
 }
 
 // k_expand_u: the square-root expansion of the knots whose Q.xx is the problem constant (stage knots
@@ -703,7 +704,7 @@ __global__ void __launch_bounds__(64) k_expand_team(const DevProblem* P, DevBuff
 // formed by team_expand's operations in its order (the Q.uu factor by the same column-distributed QR,
 // its broadcasts within the quad). The dense knots (the terminal one, knots with state rows) stay on
 // k_expand_team.
-template <class M, bool AL>
+template <class M, bool AL, bool PT>
 __device__ __forceinline__ void quad_expand(const DevProblem* P, const DevBuffers& Bf, long long b, int k, int tl) {
   using Cfg = TeamCfg<M>;
   constexpr int n = M::n, m = M::m, PU = Cfg::PU, NE = ne_of<M>(), TQ = 4;
@@ -717,7 +718,7 @@ __device__ __forceinline__ void quad_expand(const DevProblem* P, const DevBuffer
   constexpr int NXL = (n + TQ - 1) / TQ;  // Q.x entries of this lane: tl + TQ j
   double Qxs[NXL], Quuc[m], Qu[m];
   const int diag_mode = P->diag_cost;
-  const CostView C_ = cost_at<n, m>(P, k);
+  const CostView C_ = cost_at<n, m, PT>(P, k, b);
   if (diag_mode == 2) {
 #pragma unroll
     for (int j = 0; j < NXL; j++) {
@@ -780,7 +781,7 @@ __device__ __forceinline__ void quad_expand(const DevProblem* P, const DevBuffer
       rg[q] = 0.0;
       rid[q] = -1;
       if (r < p) {
-        const ConRow row = cr[r];
+        const ConRow row = traj_row<PT>(P, b, cr[r]);
         const double c = row_value<false>(row, xg, ug);
         const double l = lam[r];
         const bool act = row_inequality<false>(row) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -862,8 +863,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
   const long long b = traj_of_slot(Bf, slot, P->B);
   if (b < 0) return;  // whole teams return together (DPP broadcasts stay within a quad)
   if (!Bf.st[b].active || Bf.st[b].ls_pend) return;
-  if (ALI && P->knot_nx[k] > 0) return;  // a dense knot: k_expand_team
-  quad_expand<M, ALI != 0>(P, Bf, b, k, tl);
+  if ((ALI & 1) && P->knot_nx[k] > 0) return;  // a dense knot: k_expand_team
+  quad_expand<M, (ALI & 1) != 0, (ALI & 2) != 0>(P, Bf, b, k, tl);
 }
 
 #ifndef TOG_BWD_WAVES
@@ -968,7 +969,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
       for (int i = 0; i < n; i++) Qxc[i] = e[n + m + m * m + i + n * c];
     } else if constexpr (TV) {
-      const CostView C_ = cost_at<n, m>(P, k);
+      const CostView C_ = cost_at<n, m, false>(P, k, b);  // (Hessians only)
 #pragma unroll
       for (int i = 0; i < n; i++) Qxc[i] = SQRT ? C_.cQ[i + n * c] : C_.Q[i + n * c] * dt;
     } else {
@@ -981,7 +982,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
       for (int i = 0; i < m; i++) Quuc[i] = e[n + m + i + m * cu];
       const bool zterm = !SQRT && AL && cnt > 0;  // the std AL expansion's "+= cu'Iμcx" (an exact zero)
-      const double* Hk = TV ? cost_at<n, m>(P, k).H : P->H;
+      const double* Hk = TV ? cost_at<n, m, false>(P, k, b).H : P->H;
 #pragma unroll
       for (int i = 0; i < m; i++) {
         const double h = Hk[i + m * c] * dt;

@@ -90,6 +90,17 @@ struct DevProblem {
   const ConRow* rows;
   const int* knot_nx;   // [N] rows with a state gradient at knot k (expansion records, ne_of)
   tog_options o;
+  // Per-trajectory linear cost terms and goals (tog_set_trajectory_costs / _goals; null: the shared values
+  // above). The Hessians stay the batch's; trajectory b has its own [q; r; c] (lin: n + m + 1 doubles per
+  // trajectory, or per trajectory and stage knot, laid out (n+m+1, B) / (n+m+1, N-1, B)), its own [qf; cf]
+  // (term: (n+1, B)) and its own goal-row targets (goal: (n, B), indexed by a ROW_GOAL row's state index).
+  // A handle with any of these also carries the per-knot table kc (cost_at reads lin only beside it) and runs
+  // the time-varying kernel variants (DevBuffers::tv). Appended after every older field, whose offsets the
+  // shared-objective kernels' scalar loads keep.
+  const double* lin;
+  const double* term;
+  const double* goal;
+  int lin_per_knot, goal_ld;
 };
 
 // Read-only device tables seen through the constant address space. The row tables are read at the
@@ -184,7 +195,10 @@ struct DevBuffers {
   int spec_tail_shmem; // LDS bytes of k_ls_spec_tail's chunk image (0: the tail uses k_ls_spec)
   int spec_tail2_shmem; // LDS bytes of k_ls_spec_tail2 (two staging images + the ring; 0: not admissible)
   int cost_diag;       // DevProblem::diag_cost (host copy: kernel variants that inline the diagonal cost)
-  int tv;              // a time-varying Objective (DevProblem::kc): the team backward kernels' per-knot-cost variants
+  int tv;              // bit 0: a per-knot cost table (DevProblem::kc: a time-varying Objective, or per-trajectory
+                       // data beside the replicated shared cost): the team backward kernels' per-knot-cost variants;
+                       // bit 1: per-trajectory costs or goals (DevProblem::lin, term, goal): the PT variants of
+                       // the expansion kernels, and the rollouts' run-time-structure (DC = 0) variants
   int rows_lds;        // LDS bytes of a block's copy of the row tables (bulk k_ls_spec; 0: global tables)
   int ls_first;       // width of the first speculative round (>= nc: one round)
   int nknots;         // N (host-side launch geometry)
@@ -1316,17 +1330,52 @@ template <int n, int m>
 __host__ __device__ constexpr int kc_stride_of() {
   return 2 * n * n + 2 * m * m + m * n + n + m + 1;
 }
-template <int n, int m>
-__device__ __forceinline__ CostView cost_at(const DevProblem* P, int k) {
+// b: the trajectory (never a compacted launch's slot). With per-trajectory linear terms (DevProblem::lin) the
+// Hessians and factors are still the table's, and q, r, c are trajectory b's row, read through the global
+// address space (lane-indexed: vmcnt loads, not the flat loads of a generic pointer).
+// PT = false compiles the per-trajectory tables out (cost_at, term_at, traj_row and the cost functions below):
+// the kernels on the shared objective's hot path are instantiated so and keep their code to the instruction,
+// and a handle with per-trajectory data launches their PT variants (DevBuffers::tv bit 1).
+template <int n, int m, bool PT = true>
+__device__ __forceinline__ CostView cost_at(const DevProblem* P, int k, long long b) {
   if (!P->kc) return CostView{P->Q, P->R, P->H, P->q, P->r, P->cQ, P->cR, P->c};
-  const double* b = P->kc + (size_t)k * kc_stride_of<n, m>();
+  const double* t = P->kc + (size_t)k * kc_stride_of<n, m>();
   constexpr int oR = n * n, oH = oR + m * m, oq = oH + m * n, orr = oq + n, oc = orr + m, ocQ = oc + 1, ocR = ocQ + n * n;
-  return CostView{b, b + oR, b + oH, b + oq, b + orr, b + ocQ, b + ocR, b[oc]};
+  if (PT && P->lin) {
+    const size_t row = P->lin_per_knot ? (size_t)b * (P->N - 1) + k : (size_t)b;
+    const gptr<double> l = as_global(P->lin) + row * (n + m + 1);
+    return CostView{t, t + oR, t + oH, (const double*)l, (const double*)(l + n), t + ocQ, t + ocR, l[n + m]};
+  }
+  return CostView{t, t + oR, t + oH, t + oq, t + orr, t + ocQ, t + ocR, t[oc]};
+}
+// the terminal cost's linear and constant terms of trajectory b (DevProblem::term, else the shared qf, cf)
+struct TermView {
+  const double* qf;
+  double cf;
+};
+template <int n, bool PT = true>
+__device__ __forceinline__ TermView term_at(const DevProblem* P, long long b) {
+  if (PT && P->term) {
+    const gptr<double> t = as_global(P->term) + (size_t)b * (n + 1);
+    return TermView{(const double*)t, t[n]};
+  }
+  return TermView{P->qf, P->cf};
+}
+// A loaded constraint row as trajectory b sees it: a goal row takes its target from the goal table
+// (DevProblem::goal). Applied after the row is loaded (from the global tables or an LDS copy of them) and after
+// uniform_row: a is per lane, never wave-uniform (the team kernels hold several trajectories in a wave).
+template <bool PT = true>
+__device__ __forceinline__ ConRow traj_row(const DevProblem* P, long long b, ConRow r) {
+  if (PT && r.type == ROW_GOAL && P->goal) r.a = as_global(P->goal)[(size_t)b * P->goal_ld + r.idx];
+  return r;
 }
 
-template <int n, int m, int DC = 0>
-__device__ __forceinline__ double stage_cost_dt(const DevProblem* P, int k, const double* x, const double* u, double dt) {
-  const CostView C = cost_at<n, m>(P, k);
+// (PT defaults to DC == 0: the variants that read the cost's structure at run time also read the per-trajectory
+// tables, the ones that inline the diagonal cost are the shared objective's)
+template <int n, int m, int DC = 0, bool PT = (DC == 0)>
+__device__ __forceinline__ double stage_cost_dt(const DevProblem* P, long long b, int k, const double* x,
+                                                const double* u, double dt) {
+  const CostView C = cost_at<n, m, PT>(P, k, b);
   double xQx = 0.0, uRu = 0.0, qx = 0.0, ru = 0.0, uHx = 0.0;
   if (DC == 1 || (DC == 0 && P->diag_cost)) {
 #pragma unroll
@@ -1359,13 +1408,15 @@ __device__ __forceinline__ double stage_cost_dt(const DevProblem* P, int k, cons
   for (int i = 0; i < m; i++) ru = fma(C.r[i], u[i], ru);
   return ((((xQx + uRu) + qx) + ru) + C.c + uHx) * dt;
 }
-template <int n, int m, int DC = 0>
-__device__ __forceinline__ double stage_cost(const DevProblem* P, int k, const double* x, const double* u) {
-  return stage_cost_dt<n, m, DC>(P, k, x, u, P->dt);
+template <int n, int m, int DC = 0, bool PT = (DC == 0)>
+__device__ __forceinline__ double stage_cost(const DevProblem* P, long long b, int k, const double* x,
+                                             const double* u) {
+  return stage_cost_dt<n, m, DC, PT>(P, b, k, x, u, P->dt);
 }
 
-template <int n, int DC = 0>
-__device__ __forceinline__ double terminal_cost(const DevProblem* P, const double* x) {
+template <int n, int DC = 0, bool PT = (DC == 0)>
+__device__ __forceinline__ double terminal_cost(const DevProblem* P, long long b, const double* x) {
+  const TermView T = term_at<n, PT>(P, b);
   double xQx = 0.0, qx = 0.0;
   if (DC == 1 || (DC == 0 && P->diag_cost)) {
 #pragma unroll
@@ -1379,25 +1430,26 @@ __device__ __forceinline__ double terminal_cost(const DevProblem* P, const doubl
     }
   }
 #pragma unroll
-  for (int i = 0; i < n; i++) qx = fma(P->qf[i], x[i], qx);
-  return (xQx + qx) + P->cf;
+  for (int i = 0; i < n; i++) qx = fma(T.qf[i], x[i], qx);
+  return (xQx + qx) + T.cf;
 }
 
 // stage / terminal cost of model M: MinTimeCost for a minimum-time model (minimum_time.jl:148-149:
 // stage_cost(cost, x[1:n], u[1:m], h) + R_min_time u[end]^2 with dt = h = u[end]^2, terminal unchanged;
 // the zero-padded base matrices give the base cost of the leading parts bit for bit)
-template <class M, int DC = 0>
-__device__ __forceinline__ double stage_cost_m(const DevProblem* P, int k, const double* x, const double* u) {
+template <class M, int DC = 0, bool PT = (DC == 0)>
+__device__ __forceinline__ double stage_cost_m(const DevProblem* P, long long b, int k, const double* x,
+                                               const double* u) {
   if constexpr (ModelTraits<M>::min_time) {
     const double h = u[M::m - 1];
-    return stage_cost_dt<M::n, M::m, DC>(P, k, x, u, h * h) + P->R_min_time * (h * h);
+    return stage_cost_dt<M::n, M::m, DC, PT>(P, b, k, x, u, h * h) + P->R_min_time * (h * h);
   } else {
-    return stage_cost<M::n, M::m, DC>(P, k, x, u);
+    return stage_cost<M::n, M::m, DC, PT>(P, b, k, x, u);
   }
 }
-template <class M, int DC = 0>
-__device__ __forceinline__ double terminal_cost_m(const DevProblem* P, const double* x) {
-  return terminal_cost<M::n, DC>(P, x);
+template <class M, int DC = 0, bool PT = (DC == 0)>
+__device__ __forceinline__ double terminal_cost_m(const DevProblem* P, long long b, const double* x) {
+  return terminal_cost<M::n, DC, PT>(P, b, x);
 }
 
 // constraint row value (u == nullptr at the terminal knot: only x rows exist there)

@@ -71,8 +71,9 @@ __host__ __device__ constexpr int nq_of() {
 // AL terms λ'c + ½ c'Iμ c of one knot (augmented_lagrangian_methods.jl:298-313), rows in order. The
 // multipliers are loaded four rows at a time so their global loads overlap instead of serialising
 // one round trip per row. Ck (constraint values out) may be null.
-template <class M, class RowPtr, bool NOIDX = false>
-__device__ __forceinline__ void al_knot_terms(RowPtr rows, int cnt, const double* lamk, const double* muk,
+template <class M, bool PT = true, bool NOIDX = false, class RowPtr>
+__device__ __forceinline__ void al_knot_terms(const DevProblem* P, long long b, RowPtr rows, int cnt,
+                                              const double* lamk, const double* muk,
                                               const double* x, const double* u, double& lc, double& cIc,
                                               double* Ck) {
   for (int base = 0; base < cnt; base += 4) {
@@ -85,7 +86,7 @@ __device__ __forceinline__ void al_knot_terms(RowPtr rows, int cnt, const double
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (base + q < cnt) {
-        const ConRow r = uniform_row(load_row(rows + base + q));
+        const ConRow r = traj_row<PT>(P, b, uniform_row(load_row(rows + base + q)));
         const double c = row_value_m<M, NOIDX>(r, x, u);
         const double l = lv[q];
         const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -106,8 +107,8 @@ __device__ double traj_cost(const DevProblem* __restrict__ P, const DevBuffers& 
   constexpr int n = M::n, m = M::m;
   const int N = P->N, pmax = P->pmax;
   double J = 0.0, Jc = 0.0;
-  for (int k = 0; k < N - 1; k++) J += stage_cost_m<M>(P, k, Xs + (size_t)k * n, Us + (size_t)k * m);
-  J += terminal_cost_m<M>(P, Xs + (size_t)(N - 1) * n);
+  for (int k = 0; k < N - 1; k++) J += stage_cost_m<M>(P, b, k, Xs + (size_t)k * n, Us + (size_t)k * m);
+  J += terminal_cost_m<M>(P, b, Xs + (size_t)(N - 1) * n);
   if (!al) return J;
   const double* lam = Bf.lam + (size_t)b * N * pmax;
   const double* mu = Bf.mu + (size_t)b * N * pmax;
@@ -118,7 +119,7 @@ __device__ double traj_cost(const DevProblem* __restrict__ P, const DevBuffers& 
     const double* x = Xs + (size_t)k * n;
     const double* u = (k < N - 1) ? Us + (size_t)k * m : nullptr;
     double lc = 0.0, cIc = 0.0;
-    al_knot_terms<M>(rows, cnt, lam + (size_t)k * pmax, mu + (size_t)k * pmax, x, u, lc, cIc,
+    al_knot_terms<M>(P, b, rows, cnt, lam + (size_t)k * pmax, mu + (size_t)k * pmax, x, u, lc, cIc,
                   Cout ? Cout + (size_t)k * pmax : nullptr);
     Jc += lc + 0.5 * cIc;
   }
@@ -222,7 +223,7 @@ __device__ void expansion_gradient_entries(const DevProblem* __restrict__ P, con
     const double* u = term ? nullptr : U + (size_t)k * m;
     double q[W];
     if (!term) {
-      const CostView C_ = cost_at<n, m>(P, k);
+      const CostView C_ = cost_at<n, m>(P, k, b);
       const double dt = MT ? u[m - 1] * u[m - 1] : P->dt;
       double gx[n], gu[m];
       for (int i = 0; i < n; i++) {
@@ -241,15 +242,16 @@ __device__ void expansion_gradient_entries(const DevProblem* __restrict__ P, con
       }
       if constexpr (MT) {  // MinTimeCost (minimum_time.jl:155-188): Q.u[end] = τ(2ℓ1 + R), Q.x[end] = R x[end]
         const double R = P->R_min_time, tau = u[m - 1];
-        const double l1 = stage_cost_dt<n, m>(P, k, x, u, 1.0);
+        const double l1 = stage_cost_dt<n, m>(P, b, k, x, u, 1.0);
         q[n + m - 1] = tau * (2.0 * l1 + R);
         q[n - 1] = R * x[n - 1];
       }
     } else {
+      const TermView T_ = term_at<n>(P, b);
       for (int i = 0; i < n; i++) {
         double a = 0.0;
         for (int j = 0; j < n; j++) a = fma(P->Qf[i + n * j], x[j], a);
-        q[i] = a + P->qf[i];
+        q[i] = a + T_.qf[i];
       }
       if constexpr (MT) q[n - 1] = P->R_min_time * x[n - 1];
     }
@@ -259,7 +261,7 @@ __device__ void expansion_gradient_entries(const DevProblem* __restrict__ P, con
       double t[W];
       for (int i = 0; i < W; i++) t[i] = 0.0;
       for (int r = 0; r < p; r++) {
-        const ConRow row = load_row(rows + r);
+        const ConRow row = traj_row(P, b, load_row(rows + r));
         const double c = row_value_m<M>(row, x, u);
         const double l = lam[(size_t)k * pmax + r];
         const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(row) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -464,7 +466,7 @@ __global__ void __launch_bounds__(64) k_update_constraints(const DevProblem* __r
     const cptr<ConRow> rows = knot_rows(P, k);
     for (int i = 0; i < cnt; i++)
       Bf.C[((size_t)b * N + k) * pmax + i] =
-          row_value_m<M>(uniform_row(load_row(rows + i)), X + (size_t)k * n, k < N - 1 ? U + (size_t)k * m : nullptr);
+          row_value_m<M>(traj_row(P, b, uniform_row(load_row(rows + i))), X + (size_t)k * n, k < N - 1 ? U + (size_t)k * m : nullptr);
   }
 }
 
@@ -841,7 +843,7 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
   // minimum time: dt = τ² with τ = u[end] (MinTimeCost cost_expansion!, minimum_time.jl:155-188)
   const double dt = (MT && !term) ? sh.uk[m - 1] * sh.uk[m - 1] : P->dt;
   if (!term) {
-    const CostView C_ = cost_at<n, m>(P, k);
+    const CostView C_ = cost_at<n, m>(P, k, b);
     if (lane < n) {
       const int i = lane;
       double a = 0.0, bb = 0.0;
@@ -870,7 +872,7 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
       // the τ / h entries: ℓ1 = stage_cost(cost, x, u) (no dt), tmp = 2τ Qu
       wsync();
       const double R = P->R_min_time, tau = sh.uk[m - 1];
-      const double l1 = stage_cost_dt<n, m>(P, k, sh.xk, sh.uk, 1.0);
+      const double l1 = stage_cost_dt<n, m>(P, b, k, sh.xk, sh.uk, 1.0);
       const double w = 2.0 * l1 + R, t2 = 2.0 * tau;
       if (lane < m - 1) {
         const double tmp = t2 * sh.mtu[lane];
@@ -893,7 +895,7 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
       double a = 0.0;
 #pragma unroll
       for (int j = 0; j < n; j++) a = fma(P->Qf[lane + n * j], sh.xk[j], a);
-      sh.Qx[lane] = a + P->qf[lane];
+      sh.Qx[lane] = a + term_at<n>(P, b).qf[lane];
     }
     if constexpr (MT) {  // S.xx[end,end] = R_min_time, S.x[end] = R_min_time xN[end]
       wsync();
@@ -919,7 +921,7 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
   }
   wsync();
   for (int r = lane; r < p; r += WAVE) {  // p may exceed the wave (PCAP > 64)
-    const double c = row_value_m<M>(rows[r], sh.xk, term ? nullptr : sh.uk);
+    const double c = row_value_m<M>(traj_row(P, b, rows[r]), sh.xk, term ? nullptr : sh.uk);
     const double l = lam[r];
     const bool a = row_inequality(rows[r]) ? ((c >= 0.0) || (l > 0.0)) : true;
     const double w = a ? mu[r] : 0.0;
@@ -1986,7 +1988,7 @@ __device__ bool rollout_cost(const DevProblem* __restrict__ P, const DevBuffers&
       gsum += mx;
     }
     // stage cost and AL terms of knot k-1 (x̄_{k-1}, ū_{k-1})
-    J += stage_cost_m<M, DC>(P, k - 1, xb, ub);
+    J += stage_cost_m<M, DC>(P, b, k - 1, xb, ub);
     if (al) {
       const int cnt = RT.kcnt[k - 1];
       if (cnt) {
@@ -1995,7 +1997,7 @@ __device__ bool rollout_cost(const DevProblem* __restrict__ P, const DevBuffers&
 #pragma unroll
         for (int q = 0; q < RB; q++) {
           if (q < cnt) {
-            const ConRow r = uniform_row(load_row(rows + q));
+            const ConRow r = traj_row<DC == 0>(P, b, uniform_row(load_row(rows + q)));
             const double c = row_value_m<M>(r, xb, ub);
             const double l = lk[q];
             const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -2005,7 +2007,7 @@ __device__ bool rollout_cost(const DevProblem* __restrict__ P, const DevBuffers&
           }
         }
         if (cnt > RB)
-          al_knot_terms<M>(rows + RB, cnt - RB, lam + (size_t)(k - 1) * pmax + RB,
+          al_knot_terms<M, DC == 0>(P, b, rows + RB, cnt - RB, lam + (size_t)(k - 1) * pmax + RB,
                                                mu + (size_t)(k - 1) * pmax + RB, xb, ub, lc, cIc, nullptr);
         Jc += lc + 0.5 * cIc;
       }
@@ -2035,13 +2037,13 @@ __device__ bool rollout_cost(const DevProblem* __restrict__ P, const DevBuffers&
     }
     if (!ok) return false;
   }
-  J += terminal_cost_m<M, DC>(P, xb);
+  J += terminal_cost_m<M, DC>(P, b, xb);
   if (al) {
     const int cnt = RT.kcnt[N - 1];
     if (cnt) {
       const auto rows = RT.rows + RT.koff[N - 1];
       double lc = 0.0, cIc = 0.0;
-      al_knot_terms<M>(rows, cnt, lam + (size_t)(N - 1) * pmax, mu + (size_t)(N - 1) * pmax,
+      al_knot_terms<M, DC == 0>(P, b, rows, cnt, lam + (size_t)(N - 1) * pmax, mu + (size_t)(N - 1) * pmax,
                                            xb, nullptr, lc, cIc, nullptr);
       Jc += lc + 0.5 * cIc;
     }
@@ -2343,14 +2345,14 @@ __global__ void __launch_bounds__(64) k_ls_spec_tail(const DevProblem* __restric
         }
 #pragma unroll
         for (int i = 0; i < m; i++) __builtin_nontemporal_store(ub[i], cw + cand_at(k - 1, i, cand_q<M>(), ncp));
-        J += stage_cost_m<M, DC>(P, k - 1, xb, ub);
+        J += stage_cost_m<M, DC>(P, b, k - 1, xb, ub);
         if (al) {
           const int pc = RT.kcnt[k - 1];
           if (pc) {
             const auto rows = RT.rows + RT.koff[k - 1];
             double lc = 0.0, cIc = 0.0;
             for (int q = 0; q < pc; q++) {
-              const ConRow r = uniform_row(load_row(rows + q));
+              const ConRow r = traj_row<DC == 0>(P, b, uniform_row(load_row(rows + q)));
               const double cv = row_value_m<M, true>(r, xb, ub);
               const double l = tl[OL + c * PL + q];
               const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((cv >= 0.0) || (l > 0.0)) : true;
@@ -2385,14 +2387,14 @@ __global__ void __launch_bounds__(64) k_ls_spec_tail(const DevProblem* __restric
   if (!on) return;
   double Jj = INFINITY;
   if (live) {
-    J += terminal_cost_m<M, DC>(P, xb);
+    J += terminal_cost_m<M, DC>(P, b, xb);
     if (al) {  // terminal rows (al_knot_terms' order), multipliers from LDS
       const int pc = RT.kcnt[N - 1];
       if (pc) {
         const cptr<ConRow> rows = RT.rows + RT.koff[N - 1];
         double lc = 0.0, cIc = 0.0;
         for (int q = 0; q < pc; q++) {
-          const ConRow r = uniform_row(load_row(rows + q));
+          const ConRow r = traj_row<DC == 0>(P, b, uniform_row(load_row(rows + q)));
           const double cv = row_value_m<M, true>(r, xb, nullptr);
           const double l = tl[TCR + q];
           const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((cv >= 0.0) || (l > 0.0)) : true;
@@ -2601,7 +2603,7 @@ __global__ void __launch_bounds__(192) k_ls_spec_tail2(const DevProblem* __restr
 #pragma unroll
             for (int i = 0; i < n; i++) __builtin_nontemporal_store(x[i], cw + cand_at(s, m + i, cand_q<M>(), ncp));
           }
-          J += stage_cost_m<M, DC>(P, s, x, u);
+          J += stage_cost_m<M, DC>(P, b, s, x, u);
         }
       }
       DPROF(22);
@@ -2619,7 +2621,7 @@ __global__ void __launch_bounds__(192) k_ls_spec_tail2(const DevProblem* __restr
       for (int i = 0; i < n; i++) x[i] = ring[(size_t)i * SPEC_LANES + lane];
 #pragma unroll
       for (int i = 0; i < n; i++) __builtin_nontemporal_store(x[i], cw + cand_at(NS, m + i, cand_q<M>(), ncp));
-      if (live) J += terminal_cost_m<M, DC>(P, x);
+      if (live) J += terminal_cost_m<M, DC>(P, b, x);
     }
     __syncthreads();  // wave C's Jc
     if (on) {
@@ -2639,7 +2641,7 @@ __global__ void __launch_bounds__(192) k_ls_spec_tail2(const DevProblem* __restr
 #pragma unroll
       for (int r = 0; r < RU; r++) {
         if (r < pc) {
-          const ConRow row = uniform_row(load_row(rows + r));
+          const ConRow row = traj_row<DC == 0>(P, b, uniform_row(load_row(rows + r)));
           const double cv = row_value_m<M, true>(row, x, u);
           const double l = lp[r];
           const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(row) ? ((cv >= 0.0) || (l > 0.0)) : true;
@@ -2649,7 +2651,7 @@ __global__ void __launch_bounds__(192) k_ls_spec_tail2(const DevProblem* __restr
         }
       }
       for (int r = RU; r < pc; r++) {
-        const ConRow row = uniform_row(load_row(rows + r));
+        const ConRow row = traj_row<DC == 0>(P, b, uniform_row(load_row(rows + r)));
         const double cv = row_value_m<M, true>(row, x, u);
         const double l = lp[r];
         const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(row) ? ((cv >= 0.0) || (l > 0.0)) : true;
@@ -3009,13 +3011,13 @@ __global__ void __launch_bounds__(64) k_ls_fallback(const DevProblem* __restrict
   for (int k = lane; k < N; k += WAVE) {
     const double* x = X + (size_t)k * n;
     const double* u = (k < N - 1) ? U + (size_t)k * m : nullptr;
-    sk[k] = (k < N - 1) ? stage_cost_m<M>(P, k, x, u) : terminal_cost_m<M>(P, x);
+    sk[k] = (k < N - 1) ? stage_cost_m<M>(P, b, k, x, u) : terminal_cost_m<M>(P, b, x);
     const int cnt = al ? knot_count(P, k) : 0;
     const cptr<ConRow> rows = knot_rows(P, k);
     double lc = 0.0, cIc = 0.0;
     for (int i = 0; i < cnt; i++) {  // al_knot_terms' operations (rows differ across lanes: no uniform_row)
       const size_t q = (size_t)k * pmax + i;
-      const ConRow r = load_row(rows + i);
+      const ConRow r = traj_row(P, b, load_row(rows + i));
       const double c = row_value_m<M>(r, x, u);
       const double l = lam[q];
       const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((c >= 0.0) || (l > 0.0)) : true;
@@ -3142,14 +3144,14 @@ __global__ void __launch_bounds__(64) k_al_outer(const DevProblem* __restrict__ 
   for (int k = lane; k < N; k += WAVE) {
     const double* x = X + (size_t)k * n;
     const double* u = (k < N - 1) ? U + (size_t)k * m : nullptr;
-    sk[k] = (k < N - 1) ? stage_cost_m<M>(P, k, x, u) : terminal_cost_m<M>(P, x);
+    sk[k] = (k < N - 1) ? stage_cost_m<M>(P, b, k, x, u) : terminal_cost_m<M>(P, b, x);
     const int cnt = knot_count(P, k);
     const cptr<ConRow> rows = knot_rows(P, k);
     double lc = 0.0, cIc = 0.0, e = 0.0, im = -INFINITY;
     int ni = 0;
     for (int i = 0; i < cnt; i++) {
       const size_t q = (size_t)k * pmax + i;
-      const ConRow r = load_row(rows + i);
+      const ConRow r = traj_row(P, b, load_row(rows + i));
       const double c = row_value_m<M>(r, x, u);
       C[q] = c;
       const bool ineq = row_inequality<SL>(r);
@@ -3309,7 +3311,7 @@ __global__ void __launch_bounds__(64) k_cost_expansion(const DevProblem* __restr
   const double* u = term ? nullptr : Bf.U + ((size_t)b * (N - 1) + k) * m;
   const double dt = P->dt;
   if (!term) {  // cost.jl:183-198
-    const CostView C_ = cost_at<n, m>(P, k);
+    const CostView C_ = cost_at<n, m>(P, k, b);
     for (int i = 0; i < n; i++) {
       double a = 0.0, c = 0.0;
       for (int j = 0; j < n; j++) a = fma(C_.Q[i + n * j], x[j], a);
@@ -3327,10 +3329,11 @@ __global__ void __launch_bounds__(64) k_cost_expansion(const DevProblem* __restr
     for (int i = 0; i < m * n; i++) Qux[i] = C_.H[i] * dt;
   } else {
     for (int i = 0; i < n * n; i++) Qxx[i] = P->Qf[i];
+    const TermView T_ = term_at<n>(P, b);
     for (int i = 0; i < n; i++) {
       double a = 0.0;
       for (int j = 0; j < n; j++) a = fma(P->Qf[i + n * j], x[j], a);
-      Qx[i] = a + P->qf[i];
+      Qx[i] = a + T_.qf[i];
     }
   }
   double Wk[(W + PC) * W];  // Cholesky / QR workspace
@@ -3626,14 +3629,28 @@ struct ModelLaunch {
         const char* eq = getenv("TOG_EXPAND_QUAD");
         if (sq && !(eq && eq[0] == '0')) {
           const long long qteams = B * (long long)(N - 1);
-          if (al) hipLaunchKernelGGL((k_expand_u<M, 1>), dim3((unsigned)((qteams + 15) / 16)), dim3(64), 0, st, P, Bf);
-          else hipLaunchKernelGGL((k_expand_u<M, 0>), dim3((unsigned)((qteams + 15) / 16)), dim3(64), 0, st, P, Bf);
+          const dim3 gq((unsigned)((qteams + 15) / 16));
+          if (Bf.tv & 2) {  // (ALI bit 1: the per-trajectory variants)
+            if (al) hipLaunchKernelGGL((k_expand_u<M, 3>), gq, dim3(64), 0, st, P, Bf);
+            else hipLaunchKernelGGL((k_expand_u<M, 2>), gq, dim3(64), 0, st, P, Bf);
+          } else {
+            if (al) hipLaunchKernelGGL((k_expand_u<M, 1>), gq, dim3(64), 0, st, P, Bf);
+            else hipLaunchKernelGGL((k_expand_u<M, 0>), gq, dim3(64), 0, st, P, Bf);
+          }
           mode = (al && Bf.dense_stage_knots) ? 1 : 2;
         }
       }
       const long long teams = (mode == 2) ? B : B * (long long)N;
       const dim3 g((unsigned)((teams + TPW - 1) / TPW)), blk(64);
-      if (sq) {
+      if (Bf.tv & 2) {  // (ALI bit 1: the per-trajectory variants)
+        if (sq) {
+          if (al) hipLaunchKernelGGL((k_expand_team<M, 1, 3>), g, blk, sm, st, P, Bf, mode);
+          else hipLaunchKernelGGL((k_expand_team<M, 1, 2>), g, blk, sm, st, P, Bf, mode);
+        } else {
+          if (al) hipLaunchKernelGGL((k_expand_team<M, 0, 3>), g, blk, sm, st, P, Bf, mode);
+          else hipLaunchKernelGGL((k_expand_team<M, 0, 2>), g, blk, sm, st, P, Bf, mode);
+        }
+      } else if (sq) {
         if (al) hipLaunchKernelGGL((k_expand_team<M, 1, 1>), g, blk, sm, st, P, Bf, mode);
         else hipLaunchKernelGGL((k_expand_team<M, 1, 0>), g, blk, sm, st, P, Bf, mode);
       } else {
@@ -3647,12 +3664,15 @@ struct ModelLaunch {
                    const int* count, hipStream_t st) {
     // the tail kernels inline the diagonal cost only (the dense cost's run-time indexing of x, u would put
     // them in scratch); dense costs take k_ls_spec
-    if (Bf.tail && Bf.cand && Bf.spec_tail2_shmem > 0 && Bf.cost_diag && !list && cnt <= SPEC_LANES) {
+    // (per-trajectory costs or goals, Bf.tv bit 1, ride the run-time-structure variants, DC = 0: the kernels that
+    // inline the diagonal cost are the shared objective's and keep their code)
+    const bool diag = Bf.cost_diag && !(Bf.tv & 2);
+    if (Bf.tail && Bf.cand && Bf.spec_tail2_shmem > 0 && diag && !list && cnt <= SPEC_LANES) {
       hipLaunchKernelGGL((k_ls_spec_tail2<M, INTEG, 1>), dim3((unsigned)B), dim3(3 * WAVE),
                          (unsigned)Bf.spec_tail2_shmem, st, P, Bf, mode, lo, cnt);
       return;
     }
-    if (Bf.tail && Bf.cand && Bf.spec_tail_shmem > 0 && Bf.cost_diag && !list && cnt <= WAVE) {
+    if (Bf.tail && Bf.cand && Bf.spec_tail_shmem > 0 && diag && !list && cnt <= WAVE) {
       hipLaunchKernelGGL((k_ls_spec_tail<M, INTEG, 1>), dim3((unsigned)B), dim3(WAVE), (unsigned)Bf.spec_tail_shmem, st,
                          P, Bf, mode, lo, cnt);
       return;
@@ -3675,10 +3695,10 @@ struct ModelLaunch {
     using D1 = std::integral_constant<int, 1>;
     if (Bf.cand) {  // (the candidate-copy line search is the default path: its kernels know the diagonal cost)
       if (rb) {
-        if (Bf.cost_diag) launch(T_{}, T_{}, D1{});
+        if (diag) launch(T_{}, T_{}, D1{});
         else launch(T_{}, T_{}, D0{});
       } else {
-        if (Bf.cost_diag) launch(T_{}, F_{}, D1{});
+        if (diag) launch(T_{}, F_{}, D1{});
         else launch(T_{}, F_{}, D0{});
       }
     } else {

@@ -197,12 +197,12 @@ __device__ void pn_weights_min_time(const DevProblem* P, const PNView& w, const 
       double* wu = w.wt + (size_t)N * n + (size_t)k * m;
       const double* x = X + (size_t)k * n;
       const double* u = U + (size_t)k * m;
-      const CostView C_ = cost_at<n, m>(P, k);
+      const CostView C_ = cost_at<n, m>(P, k, 0);  // (shared objective only: tog_solve_pn refuses per-trajectory data)
       const double h = u[m - 1], dt = h * h;
       for (int i = 0; i < n - 1; i++) wx[i] = 1.0 / (C_.Q[i + n * i] * dt);
       wx[n - 1] = 1.0 / P->R_min_time;
       for (int i = 0; i < m - 1; i++) wu[i] = 1.0 / (C_.R[i + m * i] * dt);
-      const double l1 = stage_cost_dt<n, m>(P, k, x, u, 1.0);
+      const double l1 = stage_cost_dt<n, m>(P, 0, k, x, u, 1.0);
       wu[m - 1] = 1.0 / (2.0 * l1 + P->R_min_time);
     } else {
       for (int i = 0; i < n - 1; i++) wx[i] = 1.0 / P->Qf[i + n * i];
@@ -761,7 +761,7 @@ __device__ void pn_grad(const DevProblem* P, const PNView& w, const double* X, c
     double* q = w.g + (size_t)k * (n + m);
     if (k < N - 1) {
       const double* u = U + (size_t)k * m;
-      const CostView C_ = cost_at<n, m>(P, k);
+      const CostView C_ = cost_at<n, m>(P, k, 0);
       const double dt = MT ? u[m - 1] * u[m - 1] : P->dt;
       for (int i = 0; i < n; i++) {
         double a = 0.0, c = 0.0;
@@ -776,7 +776,7 @@ __device__ void pn_grad(const DevProblem* P, const PNView& w, const double* X, c
         q[n + i] = ((a + C_.r[i]) + c) * dt;
       }
       if constexpr (MT) {
-        const double l1 = stage_cost_dt<n, m>(P, k, x, u, 1.0);
+        const double l1 = stage_cost_dt<n, m>(P, 0, k, x, u, 1.0);
         q[n + m - 1] = u[m - 1] * (2.0 * l1 + P->R_min_time);
         q[n - 1] = P->R_min_time * x[n - 1];
       }

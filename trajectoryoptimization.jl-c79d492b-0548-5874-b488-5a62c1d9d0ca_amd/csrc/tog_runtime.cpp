@@ -16,6 +16,7 @@
 #include <dlfcn.h>
 
 #include "tog_plugin.hpp"
+#include "tog_traj_tables.hpp"
 #include "tog_cost_plugin.hpp"
 
 using namespace tog;
@@ -144,6 +145,15 @@ struct tog_handle {
   double *hist_in_alloc = nullptr, *hist_out_alloc = nullptr;
   int hist_cap_alloc = 0, hist_ocap_alloc = 0;
   hipEvent_t sync_ev = nullptr;  // tog_synchronize's watchdog wait
+  // per-trajectory cost terms and goals (tog_set_trajectory_costs / _goals; DevProblem::lin, term, goal): the
+  // device tables (null: the shared values), the per-knot cost table the descriptor came with (null: one stage
+  // cost, whose table row is kc_row and whose N - 1 copies are d_kc_rep once a table is set) and its variant flag
+  double *d_lin = nullptr, *d_term = nullptr, *d_goal = nullptr, *d_kc_rep = nullptr;
+  const double* kc0 = nullptr;
+  int tv0 = 0;
+  std::vector<double> kc_row;
+  std::vector<int> goal_idx;  // state index of each terminal goal row, in row order (ng = size)
+  std::string goal_err;       // why the problem's goal rows cannot vary per trajectory (empty: they can)
 };
 
 static hipEvent_t next_event(tog_handle* h) {
@@ -1021,6 +1031,17 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
     if ((rc = dalloc(h, &dkc, kc.size()))) return rc;
     HIPCHECK(hipMemcpy(dkc, kc.data(), sizeof(double) * kc.size(), hipMemcpyHostToDevice));
     P.kc = dkc;
+  } else {
+    h->kc_row = kc;  // (one row: replicated per knot when per-trajectory data is set, traj_apply)
+  }
+  h->kc0 = P.kc;
+  {
+    std::vector<int> rt(rows.size()), ri(rows.size());
+    for (size_t i = 0; i < rows.size(); i++) {
+      rt[i] = rows[i].type;
+      ri[i] = rows[i].idx;
+    }
+    h->goal_err = tog_traj::terminal_goal_rows(rt.data(), ri.data(), off.data(), cnt.data(), N, n, ROW_GOAL, h->goal_idx);
   }
   P.o = *opts;
   P.R_min_time = (d->flags & TOG_PROB_MIN_TIME) ? d->R_min_time : 0.0;
@@ -1076,6 +1097,7 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
 
   DevBuffers& b = h->buf;
   b.tv = d->stage_costs ? 1 : 0;
+  h->tv0 = b.tv;
   b.dense_stage_knots = 0;  // a stage knot with a state row (its square-root expansion changes Q.xx)
   for (int k = 0; k + 1 < N; k++)
     if (nxk[k] > 0) b.dense_stage_knots = 1;
@@ -1481,6 +1503,102 @@ int32_t tog_set_state(tog_handle* h, const double* x0, const double* U, const do
   return TOG_OK;
 }
 
+// ------------------------------------------------------------------------------ per-trajectory data
+// the handle's DevProblem after a table changed: the per-knot cost table cost_at reads the per-trajectory terms
+// beside (the descriptor's, or N - 1 copies of its one stage cost), the table pointers, the kernel variant flag
+static int32_t traj_apply(tog_handle* h) {
+  DevProblem& P = h->hostP;
+  const bool any = h->d_lin || h->d_term || h->d_goal;
+  if (any && !h->kc0 && !h->d_kc_rep) {
+    const std::vector<double> t = tog_traj::replicate_row(h->kc_row, h->N - 1);
+    int32_t rc = dalloc(h, &h->d_kc_rep, t.size());
+    if (rc) return rc;
+    HIPCHECK(hipMemcpy(h->d_kc_rep, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+  }
+  P.kc = h->kc0 ? h->kc0 : (any ? h->d_kc_rep : nullptr);
+  P.lin = h->d_lin;
+  P.term = h->d_term;
+  P.goal = h->d_goal;
+  P.goal_ld = h->n;
+  h->buf.tv = ((h->tv0 || any) ? 1 : 0) | (any ? 2 : 0);  // (bit 1: the per-trajectory kernel variants)
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
+  return TOG_OK;
+}
+// a table slot <- count doubles of src (null: drop the table); the new buffer exists before the old one goes
+static int32_t traj_table(tog_handle* h, double** slot, const double* src, size_t count) {
+  HIPCHECK(hipStreamSynchronize(h->stream));  // no kernel in flight reads the old table
+  if (!src) {
+    tog_traj::drop_buffer(slot, [&](double* p) { dfree(h, p); });
+    return TOG_OK;
+  }
+  const bool ok = tog_traj::replace_buffer(
+      slot, src, count,
+      [&](size_t c) {
+        double* p = nullptr;
+        return dalloc(h, &p, c) == TOG_OK ? p : nullptr;
+      },
+      [&](double* dst, const double* from, size_t c) {
+        return hipMemcpy(dst, from, sizeof(double) * c, hipMemcpyHostToDevice) == hipSuccess;
+      },
+      [&](double* p) { dfree(h, p); });
+  return ok ? TOG_OK : fail(TOG_ERR_DEVICE, "per-trajectory table: device allocation or copy failed");
+}
+static int32_t traj_refuse(const tog_handle* h, const char* who) {
+  if (h->ops->slack || h->ops->min_time)
+    return fail(TOG_ERR_UNSUPPORTED, std::string(who) + ": infeasible-start and minimum-time problems keep the shared "
+                                                         "objective and goal (their augmented costs and rows are built "
+                                                         "from the descriptor)");
+  return TOG_OK;
+}
+
+int32_t tog_set_trajectory_costs(tog_handle* h, int32_t per_knot, const double* lin, const double* term) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (per_knot != 0 && per_knot != 1) return fail(TOG_ERR_ARG, "per_knot must be 0 or 1");
+  if (is_multi(h)) {
+    const size_t wl = tog_traj::lin_width(h->n, h->m, h->N, per_knot), wt = tog_traj::term_width(h->n);
+    return each_part(h, [&](tog_handle* p, size_t o) {
+      return tog_set_trajectory_costs(p, per_knot, tog_traj::part_slice(lin, o, wl), tog_traj::part_slice(term, o, wt));
+    });
+  }
+  int32_t rc = traj_refuse(h, "tog_set_trajectory_costs");
+  if (rc) return rc;
+  HIPCHECK(hipSetDevice(h->device));
+  const size_t B = (size_t)h->B;
+  rc = traj_table(h, &h->d_lin, lin, B * tog_traj::lin_width(h->n, h->m, h->N, per_knot));
+  if (!rc) {
+    h->hostP.lin_per_knot = lin ? per_knot : 0;
+    rc = traj_table(h, &h->d_term, term, B * tog_traj::term_width(h->n));
+  }
+  // (also after a failure: the device's DevProblem must never keep a pointer to a table that was replaced)
+  const int32_t ra = traj_apply(h);
+  return rc ? rc : ra;
+}
+
+int32_t tog_set_trajectory_goals(tog_handle* h, const double* xf) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (is_multi(h)) {
+    const size_t ng = h->parts[0]->goal_idx.size();
+    return each_part(h, [&](tog_handle* p, size_t o) {
+      return tog_set_trajectory_goals(p, tog_traj::part_slice(xf, o, ng));
+    });
+  }
+  int32_t rc = traj_refuse(h, "tog_set_trajectory_goals");
+  if (rc) return rc;
+  if (h->goal_idx.empty() && h->goal_err.empty())
+    return fail(TOG_ERR_ARG, "tog_set_trajectory_goals: the problem's terminal set has no goal constraint");
+  if (!h->goal_err.empty()) return fail(TOG_ERR_UNSUPPORTED, h->goal_err);
+  HIPCHECK(hipSetDevice(h->device));
+  if (xf) {
+    const std::vector<double> t = tog_traj::goal_table(xf, h->goal_idx, h->n, h->B);
+    rc = traj_table(h, &h->d_goal, t.data(), t.size());
+  } else {
+    rc = traj_table(h, &h->d_goal, nullptr, 0);
+  }
+  const int32_t ra = traj_apply(h);
+  return rc ? rc : ra;
+}
+
 // ------------------------------------------------------------------------------ step level
 int32_t tog_rollout_open_loop(tog_handle* h) {
   if (!h) return fail(TOG_ERR_ARG, "null handle");
@@ -1863,6 +1981,9 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
       return tog_solve_pn(p, opts, out ? out + o * TOG_PN_NSTATS : nullptr);
     });
   if (opts->solve_type != 0 && opts->solve_type != 1) return fail(TOG_ERR_ARG, "solve_type must be 0 (:feasible) or 1 (:optimal)");
+  if (h->d_lin || h->d_term || h->d_goal)
+    return fail(TOG_ERR_UNSUPPORTED, "tog_solve_pn: per-trajectory costs or goals are set (projected Newton reads the "
+                                     "shared objective and goal; clear them with NULL tables first)");
   const bool optimal = opts->solve_type == 1;
   if (opts->n_steps < 0) return fail(TOG_ERR_ARG, "n_steps must be >= 0");
   if (!h->ops->pn) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");

@@ -101,6 +101,56 @@ class BatchHandle:
             # a partially finite X0: upload as given (rollout!(prob) will trigger on the NaNs)
             Xp = abi.as_dp(X)
         abi.check(self.lib, self.lib.tog_set_state(self.h, abi.as_dp(x0), abi.as_dp(U), Xp))
+        self.upload_trajectory_data(prob)
+
+    # ------------------------------------------------------------------ per-trajectory costs and goals
+    def upload_trajectory_data(self, prob):
+        """The problem's BatchObjective tables and per-trajectory goals. A part the problem does not have goes
+        back to the shared values if the handle holds a table for it (a handle that never held one is not
+        touched)."""
+        obj = getattr(prob, "obj", None)
+        if hasattr(obj, "lin"):
+            self.set_trajectory_costs(obj.lin, obj.term)
+        elif getattr(self, "_traj_costs", False):
+            self.set_trajectory_costs(None, None)
+        goals = prob.trajectory_goals() if hasattr(prob, "trajectory_goals") else None
+        if goals is not None:
+            self.set_trajectory_goals(goals)
+        elif getattr(self, "_traj_goals", False):
+            self.set_trajectory_goals(None)
+
+    def set_trajectory_costs(self, lin=None, term=None):
+        """tog_set_trajectory_costs. lin: (B, n+m+1) rows [q; r; c], or (B, N-1, n+m+1) with a row per stage
+        knot; term: (B, n+1) rows [qf; cf]. None: that part stays shared (both None: the shared objective)."""
+        n, m, N, B = self.n, self.m, self.N, self.B
+        null = C.cast(None, C.POINTER(C.c_double))
+        per_knot, lp, tp = 0, null, null
+        if lin is not None:
+            lin = np.ascontiguousarray(lin, dtype=np.float64)
+            if lin.shape == (B, N - 1, n + m + 1):
+                per_knot = 1
+            elif lin.shape != (B, n + m + 1):
+                raise ValueError(f"lin must be ({B}, {n + m + 1}) or ({B}, {N - 1}, {n + m + 1}), got {lin.shape}")
+            lp = abi.as_dp(lin)
+        if term is not None:
+            term = np.ascontiguousarray(term, dtype=np.float64)
+            if term.shape != (B, n + 1):
+                raise ValueError(f"term must be ({B}, {n + 1}), got {term.shape}")
+            tp = abi.as_dp(term)
+        abi.check(self.lib, self.lib.tog_set_trajectory_costs(self.h, per_knot, lp, tp))
+        self._traj_costs = lin is not None or term is not None
+
+    def set_trajectory_goals(self, xf=None):
+        """tog_set_trajectory_goals. xf: (B, ng) values of the terminal goal rows; None: the descriptor's."""
+        if xf is None:
+            abi.check(self.lib, self.lib.tog_set_trajectory_goals(self.h, C.cast(None, C.POINTER(C.c_double))))
+            self._traj_goals = False
+            return
+        xf = np.ascontiguousarray(xf, dtype=np.float64)
+        if xf.ndim != 2 or xf.shape[0] != self.B:
+            raise ValueError(f"xf must be ({self.B}, ng), got {xf.shape}")
+        abi.check(self.lib, self.lib.tog_set_trajectory_goals(self.h, abi.as_dp(xf)))
+        self._traj_goals = True
 
     def download_state(self, prob):
         prob._X[...] = self.get(abi.FIELD_X)

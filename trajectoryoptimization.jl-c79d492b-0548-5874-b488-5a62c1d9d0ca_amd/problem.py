@@ -515,6 +515,62 @@ def LQRObjective(Q, R, Qf, xf, N) -> Objective:
     return Objective([ell] * (N - 1) + [ellN])
 
 
+class BatchObjective(Objective):
+    """B Objectives in one batch, one per trajectory, that share every Hessian (Q, R, H at each stage knot, Qf)
+    and differ in the linear and constant terms: what ``LQRObjective(Q, R, Qf, xf_b, N)`` gives a batch of goals,
+    or a tracking cost a batch of references. As an Objective it is trajectory 0's (the problem descriptor's);
+    ``self[b]`` is trajectory b's Objective, ``lin`` / ``term`` the tables of tog_set_trajectory_costs:
+    ``lin`` (B, n+m+1) rows [q; r; c] (``per_knot`` False) or (B, N-1, n+m+1), ``term`` (B, n+1) rows [qf; cf]."""
+
+    def __init__(self, objs):
+        objs = list(objs)
+        if not objs:
+            raise ValueError("BatchObjective needs at least one Objective")
+        o0 = objs[0]
+        super().__init__(list(o0.cost))
+        for b, o in enumerate(objs):
+            if len(o) != len(o0):
+                raise ValueError(f"trajectory {b}: objective length {len(o)} != {len(o0)}")
+            for k, (c, c0) in enumerate(zip(o.cost, o0.cost)):
+                if not isinstance(c, QuadraticCost):
+                    raise ValueError(f"trajectory {b}, knot {k}: a BatchObjective holds QuadraticCosts")
+                for f in ("Q", "R", "H"):
+                    if not np.array_equal(getattr(c, f), getattr(c0, f)):
+                        raise ValueError(f"trajectory {b}, knot {k}: Hessian {f} differs from trajectory 0's "
+                                         "(a batch shares its Hessians; only q, r, c may differ)")
+        self.objs = objs
+        self.per_knot = any(o.varying for o in objs)
+        n = o0.stage.Q.shape[0]
+        m = max(c.r.size for o in objs for c in o.cost[:-1])
+
+        def row(c):
+            r = c.r if c.r.size else np.zeros(m)
+            return np.concatenate([c.q, r, [c.c]])
+
+        if self.per_knot:
+            self.lin = np.stack([np.stack([row(c) for c in o.cost[:-1]]) for o in objs])
+        else:
+            self.lin = np.stack([row(o.stage) for o in objs])
+        self.term = np.stack([np.concatenate([o.terminal.q, [o.terminal.c]]) for o in objs])
+        assert self.term.shape == (len(objs), n + 1)
+
+    @property
+    def B(self):
+        return len(self.objs)
+
+    def __getitem__(self, b):
+        return self.objs[b]
+
+
+def LQRObjectiveBatch(Q, R, Qf, XF, N) -> BatchObjective:
+    """``LQRObjective(Q, R, Qf, XF[b], N)`` for every row of XF (B, n), as one BatchObjective: each member is built
+    by LQRObjective itself, so a trajectory's q, c, qf, cf are bit for bit a single-goal problem's."""
+    XF = np.asarray(XF, dtype=np.float64)
+    if XF.ndim != 2:
+        raise ValueError("XF must be (B, n)")
+    return BatchObjective([LQRObjective(Q, R, Qf, xf, N) for xf in XF])
+
+
 # ----------------------------------------------------------------------------- constraints
 
 
@@ -639,16 +695,29 @@ class GoalConstraint(_Constraint):
     label = "goal"
 
     def __init__(self, xf):
+        # (B, n): a goal per trajectory (tog_set_trajectory_goals); the descriptor carries trajectory 0's
         self.xf = np.asarray(xf, dtype=np.float64).copy()
+        if self.xf.ndim not in (1, 2):
+            raise ValueError("goal_constraint: xf must be (n,) or (B, n)")
+
+    @property
+    def batched(self):
+        return self.xf.ndim == 2
+
+    def for_traj(self, b):
+        """trajectory b's plain goal constraint"""
+        return GoalConstraint(self.xf[b]) if self.batched else self
 
     def length(self, kind="stage"):
-        return 0 if kind == "stage" else len(self.xf)
+        return 0 if kind == "stage" else self.xf.shape[-1]
 
     def evaluate(self, x, u=None):
-        return np.asarray(x, dtype=np.float64) - self.xf if u is None else np.zeros(0)
+        xf = self.xf[0] if self.batched else self.xf
+        return np.asarray(x, dtype=np.float64) - xf if u is None else np.zeros(0)
 
     def to_abi(self):
-        return (abi.CON_GOAL, len(self.xf), self.xf)  # count: the goal rows x[1:count] - xf (inds, constraints.jl:303)
+        xf = np.ascontiguousarray(self.xf[0] if self.batched else self.xf)
+        return (abi.CON_GOAL, len(xf), xf)  # count: the goal rows x[1:count] - xf (inds, constraints.jl:303)
 
 
 def goal_constraint(xf):
@@ -842,10 +911,11 @@ class Problem:
         self.batched = x0.ndim == 2
         B = x0.shape[0] if self.batched else 1
         self.x0 = x0.reshape(B, n).copy()
-        self.xf = np.zeros(n) if xf is None else np.asarray(xf, dtype=np.float64).copy()
+        self.xf = np.zeros(n) if xf is None else np.asarray(xf, dtype=np.float64).copy()  # (n,) or (B, n)
         self.N, self.dt, self.tf = N, dt, tf
         self._X = np.full((B, N, n), np.nan)
         self._U = np.zeros((B, N - 1, m))
+        self.check_trajectory_data()
         if U0 is not None:
             initial_controls_b(self, U0)
         if X0 is not None:
@@ -886,6 +956,49 @@ class Problem:
 
     def is_constrained(self):
         return self.constraints.is_constrained()
+
+    # ---- per-trajectory objectives and goals
+    def trajectory_goals(self):
+        """(B, ng) goal values of the terminal set's per-trajectory goal constraint, or None."""
+        for c in self.constraints[self.N - 1]:
+            if isinstance(c, GoalConstraint) and c.batched:
+                return c.xf
+        return None
+
+    def has_trajectory_data(self) -> bool:
+        return isinstance(self.obj, BatchObjective) or self.trajectory_goals() is not None
+
+    def check_trajectory_data(self):
+        """shapes of the per-trajectory data against the batch (ValueError)"""
+        B, n = self.B, self.model.n
+        if isinstance(self.obj, BatchObjective) and self.obj.B != B:
+            raise ValueError(f"BatchObjective holds {self.obj.B} objectives, the problem {B} trajectories")
+        if self.xf.ndim == 2 and self.xf.shape != (B, n):
+            raise ValueError(f"xf must be (n,) or (B, n) = ({B}, {n}), got {self.xf.shape}")
+        for k in range(self.N):
+            for c in self.constraints[k]:
+                if isinstance(c, GoalConstraint) and c.batched:  # (rows at the terminal knot only)
+                    if c.xf.shape[0] != B:
+                        raise ValueError(f"goal_constraint holds {c.xf.shape[0]} goals, the problem {B} trajectories")
+
+    def trajectory(self, b: int) -> "Problem":
+        """The plain B = 1 problem of trajectory b: its objective, goal, x0, U, X."""
+        if not 0 <= b < self.B:
+            raise IndexError(f"trajectory {b} of {self.B}")
+        p = _copy.copy(self)
+        p.obj = self.obj[b] if isinstance(self.obj, BatchObjective) else self.obj
+        p.constraints = _copy_constraints(self.constraints)
+        memo = {}  # (one plain goal constraint per batched one: knots that share a set keep sharing it)
+        for k in range(self.N):
+            p.constraints.C[k] = ConstraintSet(
+                memo.setdefault(id(c), c.for_traj(b)) if isinstance(c, GoalConstraint) else c
+                for c in self.constraints[k])
+        p.batched = False
+        p.x0 = self.x0[b:b + 1].copy()
+        p.xf = (self.xf[b] if self.xf.ndim == 2 else self.xf).copy()
+        p._X = self._X[b:b + 1].copy()
+        p._U = self._U[b:b + 1].copy()
+        return p
 
     # ---- marshalling to the C ABI
     def build_desc(self, tf_min: bool = False) -> abi.DescBuilder:
@@ -983,6 +1096,8 @@ def max_violation(prob: Problem) -> float:
                 term = k == N - 1
                 vals_e, vals = [], []
                 for c in cs:
+                    if isinstance(c, GoalConstraint):
+                        c = c.for_traj(b)  # (a goal per trajectory)
                     v = c.evaluate(X[k]) if term else c.evaluate(X[k], U[k])
                     if len(v) == 0:
                         continue

@@ -7,9 +7,9 @@ import math
 
 import numpy as np
 
-from .problem import (BoundConstraint, CircleConstraints, Constraints, Dynamics, LQRCost, LQRCostTerminal,
-                      LQRObjective, Objective, Problem, discretize_model, infeasible_problem,
-                      SphereConstraints, goal_constraint, rk3, rk4)
+from .problem import (BoundConstraint, CircleConstraints, Constraints, ConstraintSet, Dynamics, GoalConstraint,
+                      LQRCost, LQRCostTerminal, LQRObjective, LQRObjectiveBatch, Objective, Problem, discretize_model,
+                      infeasible_problem, SphereConstraints, goal_constraint, rk3, rk4)
 from .solvers import ALTROSolverOptions, AugmentedLagrangianSolverOptions, iLQRSolverOptions
 
 HOVER = 0.5 * 9.81 / 4.0
@@ -316,6 +316,26 @@ def config_quadrotor(B=8192, offset=0):
     opts_al = AugmentedLagrangianSolverOptions(opts_uncon=opts_ilqr, constraint_tolerance=1e-3,
                                                cost_tolerance=1e-5, cost_tolerance_intermediate=1e-4)
     return prob, opts_al
+
+
+def config_quadrotor_goals(B=8192, offset=0):
+    """Config 3 with a goal per trajectory: xf[b][1:3] = config 3's goal position + U(-1, 1)^3 (seed 3000+b).
+    Both the LQR cost's goal (a BatchObjective: q, c, qf, cf per trajectory) and the goal constraint's rows
+    differ per trajectory; x0, U0 and the options are config 3's."""
+    prob, opts = config_quadrotor(B=B, offset=offset)
+    N = prob.N
+    st, term = prob.obj.stage, prob.obj.terminal
+    D = _per_traj_rng(3000 + offset, B, lambda r: r.uniform(-1.0, 1.0, 3))
+    XF = np.tile(prob.xf, (B, 1))
+    XF[:, 0:3] += D
+    obj = LQRObjectiveBatch(st.Q, st.R, term.Q, XF, N)
+    goal = goal_constraint(XF)
+    cons = Constraints(N)
+    for k in range(N):
+        cons[k] = ConstraintSet(goal if isinstance(c, GoalConstraint) else c for c in prob.constraints[k])
+    out = Problem(prob.model, obj, constraints=cons, x0=prob.x0, xf=XF, N=N, dt=prob.dt)
+    out._U[...] = prob._U
+    return out, opts
 
 
 def config_quadrotor_tv(B=8192, offset=0):

@@ -369,6 +369,7 @@ class ProjectedNewtonSolver(AbstractSolver):
 
     def __init__(self, prob, opts: ProjectedNewtonSolverOptions | None = None, **kw):
         opts = ProjectedNewtonSolverOptions() if opts is None else opts
+        _refuse_trajectory_data(prob, "ProjectedNewtonSolver")
         super().__init__(prob, iLQRSolverOptions(), **kw)
         self.opts = opts
         self.handle.upload_state(prob)
@@ -432,11 +433,21 @@ def _raise_pn_errors(flags, solver):
                                    f"{bad.tolist()} (the reference's _projection_linesearch! raises here)", bad, solver)
 
 
+def _refuse_trajectory_data(prob, who):
+    """ALTRO's descriptor-level transforms and projected Newton read the shared objective and goal: a problem
+    with a BatchObjective or per-trajectory goals is refused before anything reaches the device."""
+    if getattr(prob, "has_trajectory_data", None) and prob.has_trajectory_data():
+        raise ValueError(f"{who}: the problem has per-trajectory costs or goals (BatchObjective, goal_constraint "
+                         "(B, n)); solve it with iLQRSolverOptions or AugmentedLagrangianSolverOptions, or one "
+                         "goal at a time through Problem.trajectory(b)")
+
+
 def AbstractSolverFor(prob, opts, **kw):
     """``AbstractSolver(prob, opts)`` dispatch on the options type (src/solvers.jl:60-62)."""
     if isinstance(opts, iLQRSolverOptions):
         return iLQRSolver(prob, opts, **kw)
     if isinstance(opts, ALTROSolverOptions):
+        _refuse_trajectory_data(prob, "ALTROSolver")
         _altro_pn_tolerances(opts)
         return ALTROSolver(prob, opts, **kw)
     if isinstance(opts, ProjectedNewtonSolverOptions):
@@ -564,6 +575,7 @@ def solve_b(prob, solver_or_opts, *, max_steps: int | None = None, device: int =
     ``history``: record the per-iteration statistics (``solver.traj_stats(b)``): None = on with
     ``history_capacity`` records per trajectory, False = off, an int = that capacity."""
     if isinstance(solver_or_opts, ProjectedNewtonSolver):
+        _refuse_trajectory_data(prob, "ProjectedNewtonSolver")
         solver_or_opts.handle.upload_state(prob)
         return _solve_pn(prob, solver_or_opts)
     if isinstance(solver_or_opts, AbstractSolver):
@@ -574,6 +586,7 @@ def solve_b(prob, solver_or_opts, *, max_steps: int | None = None, device: int =
         if isinstance(opts, ProjectedNewtonSolverOptions):
             return _solve_pn(prob, ProjectedNewtonSolver(prob, opts, device=device))
         if isinstance(opts, ALTROSolverOptions):
+            _refuse_trajectory_data(prob, "ALTROSolverOptions")
             _altro_pn_tolerances(opts)  # (mutates opts.opts_al, as the reference does)
             return _solve_altro(prob, opts, device, max_steps=max_steps, history=history)
         if isinstance(opts, AugmentedLagrangianSolverOptions) and not prob.is_constrained():
