@@ -1,7 +1,7 @@
 // Stand-alone host check of csrc/tog_traj_tables.hpp (the host side of tog_set_trajectory_costs / _goals): the
 // slices a multi-device handle hands to its parts, the goal table's expansion, the per-knot replication, the
-// terminal goal row scan and the replace order of a device buffer (new before old), with heap buffers in the
-// place of device memory. Built with -fsanitize=address,undefined by tests/test_trajectory_goals.py; it has no
+// terminal goal row scan and the replace order of a device buffer, alone and as tog_history_enable's pair (new
+// before old), with heap buffers in the place of device memory. Built with -fsanitize=address,undefined by tests/test_trajectory_goals.py; it has no
 // device code and needs no GPU. Exit status 0 and "ok" on success.
 #include <cstdio>
 #include <cstdlib>
@@ -133,6 +133,44 @@ int main() {
     drop_buffer(&slot, release);
     CHECK(slot == nullptr && live == 0);
     drop_buffer(&slot, release);  // (null: nothing)
+    CHECK(live == 0);
+  }
+
+  // a pair replaced together (tog_history_enable's grow): both new buffers before the old ones go; an allocator
+  // that fails on its first call, and one that fails on its second, leave the slots and the old buffers alone and
+  // leak nothing (the leak check sees a fresh buffer that was not released)
+  {
+    int live = 0, calls = 0, fail_at = 0;  // fail_at: the call of alloc that returns null (0: none)
+    double *old_a = nullptr, *old_b = nullptr;
+    bool old_alive_at_alloc = true;
+    auto alloc = [&](size_t c) -> double* {
+      if (old_a) old_alive_at_alloc = old_alive_at_alloc && old_a[0] == 1.0 && old_b[0] == 2.0;  // reads the old ones
+      if (++calls == fail_at) return nullptr;
+      live++;
+      return (double*)std::malloc(sizeof(double) * (c ? c : 1));
+    };
+    auto release = [&](double* p) {
+      live--;
+      std::free(p);
+    };
+    double *a = nullptr, *b = nullptr;
+    CHECK(replace_buffer_pair(&a, 6, &b, 8, alloc, release) && a && b && a != b && live == 2);  // first enable
+    a[0] = a[5] = 1.0;
+    b[0] = b[7] = 2.0;
+    old_a = a;
+    old_b = b;
+    for (fail_at = 1; fail_at <= 2; fail_at++) {
+      calls = 0;
+      CHECK(!replace_buffer_pair(&a, 60, &b, 80, alloc, release));
+      CHECK(a == old_a && b == old_b && live == 2 && calls == fail_at);
+      CHECK(a[5] == 1.0 && b[7] == 2.0);  // the old buffers were not released
+    }
+    fail_at = 0;
+    CHECK(replace_buffer_pair(&a, 60, &b, 80, alloc, release) && a != old_a && b != old_b && live == 2);  // grow
+    CHECK(old_alive_at_alloc);
+    a[59] = b[79] = 3.0;  // the new sizes
+    release(a);
+    release(b);
     CHECK(live == 0);
   }
 

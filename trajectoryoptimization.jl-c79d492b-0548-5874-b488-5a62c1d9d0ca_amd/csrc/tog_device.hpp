@@ -16,7 +16,8 @@
 #include "../../include/tog_math.h"
 #include "../../include/tog_kuka.h"
 
-// Hash of the text of every libtog header (the Makefile's HDRS, in order; abi.header_hash() computes
+// Hash of the text of every libtog header (the Makefile's HDRS, in order: the kernels, the launch table
+// tog_launch.hpp and the host-only tog_host_plan.hpp / tog_traj_tables.hpp alike; abi.header_hash() computes
 // the same value for plugins generated at run time). libtog and every plugin are compiled with it and
 // the plugin fingerprints include it, so tog_model_load / tog_generic_cost_load refuse a plugin built
 // against other headers.
@@ -210,9 +211,8 @@ struct DevBuffers {
   int* ls_win;        // (B) accepted trial of the current forward pass (k_ls_decide)
   double* ls_Jw;      // (B) its cost
   double* gk;         // (N, B) per-knot todorov gradient terms of the accepted Ū
-  double* jws;        // Kuka RK3 Jacobian workspace (stage-chain form: KJ_WSK doubles per knot slot; the
-                      // dual-staged A/B form: 2n duals per lane), or null
-  int jac_chain;      // Kuka RK3 Jacobian in stage-chain form (tog_kuka_jac.hpp; 0: TOG_KUKA_JAC=dual A/B)
+  double* jws;        // Kuka RK3 Jacobian workspace (stage-chain form, tog_kuka_jac.hpp: KJ_WSK doubles per knot
+                      // slot), or null
   int dense_stage_knots;  // some stage knot has a state-gradient row (k_expand_u / k_expand_team split)
   // compacted tail launches (tog_solve_step, k_list_active): the step's active trajectories and their
   // count; null outside a tail step (launch slot = trajectory index)

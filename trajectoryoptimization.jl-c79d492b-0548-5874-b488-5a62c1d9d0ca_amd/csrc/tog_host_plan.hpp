@@ -1,0 +1,155 @@
+// Host arithmetic that decides which kernel code a handle runs (tog_create): the run-time flag -> template
+// constant dispatcher of the launch table (tog_launch.hpp), the stage-cost table with its Cholesky factors and
+// diagonal-cost class, and the Q.xx pattern of the packed expansion records. Plain C++ with no device runtime in
+// it, so that a stand-alone program can run it under the host sanitizers (tests/c/host_plan_host.cpp).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+namespace tog_plan {
+
+// a run-time value -> the compile-time constant among Vs it equals: f(std::integral_constant<int, v>{})
+// (f runs once when v is in Vs and never otherwise)
+template <int... Vs, class F>
+inline void pick(int v, F&& f) {
+  (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// upper Cholesky (dpotrf 'U') of a symmetric matrix; returns false if not PD
+inline bool chol_upper(const double* A, int n, double* U) {
+  for (int i = 0; i < n * n; i++) U[i] = 0.0;
+  for (int j = 0; j < n; j++) {
+    double s = A[j + n * j];
+    for (int k = 0; k < j; k++) s -= U[k + n * j] * U[k + n * j];
+    if (!(s > 0.0)) return false;
+    const double ujj = std::sqrt(s);
+    U[j + n * j] = ujj;
+    for (int c = j + 1; c < n; c++) {
+      double t = A[j + n * c];
+      for (int k = 0; k < j; k++) t -= U[k + n * j] * U[k + n * c];
+      U[j + n * c] = t / ujj;
+    }
+  }
+  return true;
+}
+
+// The stage cost(s) of a problem: one for every knot, or a time-varying Objective's table (rows
+// [Q; R; H; q; r; c], nc_in doubles each). The device table (DevProblem::kc) adds each knot's square-root
+// factors: row k is [Q; R; H; q; r; c; cQ; cR] with cQ = chol(Q dt), cR = chol(R dt), kst doubles.
+struct CostPlan {
+  int nc_in = 0, kst = 0, nk = 0;  // nk rows: N - 1 with a table, else 1
+  int n = 0, m = 0;
+  std::vector<double> kc;   // (kst, nk)
+  std::vector<double> cQf;  // chol(Qf), (n, n)
+  bool sqrt_ok = false;     // every Hessian is PD
+  // 0 dense; 1 diagonal Q/R/Qf, H = 0; 2 = 1 with every off-diagonal entry (and H, and the factors'
+  // off-diagonals) +0.0 and dt > 0, so the kernels may use literal zeros for them and stay bit-identical
+  int diag_cost = 0;
+  const double* Q(int k) const { return kc.data() + (size_t)k * kst; }
+  const double* R(int k) const { return Q(k) + n * n; }
+  const double* H(int k) const { return R(k) + m * m; }
+  const double* q(int k) const { return H(k) + m * n; }
+  const double* r(int k) const { return q(k) + n; }
+  double c(int k) const { return Q(k)[nc_in - 1]; }
+  const double* cQ(int k) const { return Q(k) + nc_in; }
+  const double* cR(int k) const { return cQ(k) + n * n; }
+};
+
+// stage_costs: the (nc_in, N - 1) table, or null for the shared Q, R, H, q, r, c
+inline CostPlan plan_costs(int n, int m, int N, double dt, const double* Q, const double* R, const double* H,
+                           const double* q, const double* r, double c, const double* stage_costs,
+                           const double* Qf) {
+  CostPlan p;
+  p.n = n;
+  p.m = m;
+  p.nc_in = n * n + m * m + m * n + n + m + 1;
+  p.kst = 2 * n * n + 2 * m * m + m * n + n + m + 1;
+  p.nk = stage_costs ? N - 1 : 1;
+  const int nc_in = p.nc_in, nk = p.nk;
+  p.kc.assign((size_t)nk * p.kst, 0.0);
+  for (int k = 0; k < nk; k++) {
+    double* o = p.kc.data() + (size_t)k * p.kst;
+    if (stage_costs) {
+      memcpy(o, stage_costs + (size_t)k * nc_in, sizeof(double) * nc_in);
+    } else {
+      memcpy(o, Q, sizeof(double) * n * n);
+      memcpy(o + n * n, R, sizeof(double) * m * m);
+      memcpy(o + n * n + m * m, H, sizeof(double) * m * n);
+      memcpy(o + n * n + m * m + m * n, q, sizeof(double) * n);
+      memcpy(o + n * n + m * m + m * n + n, r, sizeof(double) * m);
+      o[nc_in - 1] = c;
+    }
+  }
+  auto kcQ = [&](int k) { return p.kc.data() + (size_t)k * p.kst + nc_in; };
+  auto kcR = [&](int k) { return kcQ(k) + n * n; };
+  p.cQf.assign((size_t)n * n, 0.0);
+  bool ok = chol_upper(Qf, n, p.cQf.data());
+  std::vector<double> Qdt((size_t)n * n), Rdt((size_t)m * m);
+  for (int k = 0; k < nk; k++) {
+    for (int i = 0; i < n * n; i++) Qdt[i] = p.Q(k)[i] * dt;
+    for (int i = 0; i < m * m; i++) Rdt[i] = p.R(k)[i] * dt;
+    ok = chol_upper(Qdt.data(), n, kcQ(k)) && chol_upper(Rdt.data(), m, kcR(k)) && ok;
+  }
+  p.sqrt_ok = ok;
+  bool diag = true;
+  for (int j = 0; j < n; j++)
+    for (int i = 0; i < n; i++)
+      if (i != j && Qf[i + n * j] != 0.0) diag = false;
+  for (int k = 0; k < nk; k++) {
+    for (int j = 0; j < n; j++)
+      for (int i = 0; i < n; i++)
+        if (i != j && p.Q(k)[i + n * j] != 0.0) diag = false;
+    for (int j = 0; j < m; j++)
+      for (int i = 0; i < m; i++)
+        if (i != j && p.R(k)[i + m * j] != 0.0) diag = false;
+    for (int i = 0; i < m * n; i++)
+      if (p.H(k)[i] != 0.0) diag = false;
+  }
+  bool pz = diag && dt > 0.0;
+  auto offdiag_pz = [&](const double* A, int kk) {
+    for (int j = 0; j < kk; j++)
+      for (int i = 0; i < kk; i++)
+        if (i != j && (A[i + kk * j] != 0.0 || std::signbit(A[i + kk * j]))) return false;
+    return true;
+  };
+  if (pz) pz = offdiag_pz(Qf, n) && (!ok || offdiag_pz(p.cQf.data(), n));
+  for (int k = 0; pz && k < nk; k++) {
+    pz = offdiag_pz(p.Q(k), n) && offdiag_pz(p.R(k), m);
+    if (pz && ok) pz = offdiag_pz(p.cQ(k), n) && offdiag_pz(p.cR(k), m);
+    for (int i = 0; pz && i < m * n; i++)
+      if (std::signbit(p.H(k)[i])) pz = false;
+  }
+  p.diag_cost = diag ? (pz ? 2 : 1) : 0;
+  return p;
+}
+
+// Packed std AL expansion records: the Q.xx entries a constraint row can change. masks: one per row, a bit per
+// state index with a non-zero gradient entry. qpat[c]: a bit per row i of column c (the union over the rows of
+// (state indices)^2), qoff[c] its running count, qpat_n the total, qpat_max the most entries in one column.
+struct QPattern {
+  std::vector<unsigned int> qpat;
+  std::vector<int> qoff;
+  int qpat_n = 0, qpat_max = 0;
+};
+inline QPattern plan_qpattern(int n, const unsigned int* masks, size_t nmasks) {
+  QPattern p;
+  p.qpat.assign((size_t)n, 0u);
+  p.qoff.assign((size_t)n, 0);
+  for (size_t r = 0; r < nmasks; r++)
+    for (int c = 0; c < n; c++)
+      if (masks[r] >> c & 1u) p.qpat[(size_t)c] |= masks[r];
+  int off = 0;
+  for (int c = 0; c < n; c++) {
+    p.qoff[(size_t)c] = off;
+    off += __builtin_popcount(p.qpat[(size_t)c]);
+    p.qpat_max = std::max(p.qpat_max, __builtin_popcount(p.qpat[(size_t)c]));
+  }
+  p.qpat_n = off;
+  return p;
+}
+
+}  // namespace tog_plan

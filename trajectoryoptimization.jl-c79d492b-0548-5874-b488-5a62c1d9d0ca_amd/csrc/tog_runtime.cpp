@@ -16,39 +16,33 @@
 #include <dlfcn.h>
 
 #include "tog_plugin.hpp"
+#include "tog_host_plan.hpp"
 #include "tog_traj_tables.hpp"
 #include "tog_cost_plugin.hpp"
 
 using namespace tog;
 
+// The built-in models: X(model id, unit suffix). Each has four translation units, k_<suffix>.hip (ops_<suffix>),
+// k_inf_<suffix>.hip (add_slack_controls(model): infeasible start, src/model.jl:761-779), k_mt_<suffix>.hip
+// (add_min_time_controls(model): minimum time, src/solvers/altro/minimum_time.jl:83-104) and k_mtinf_<suffix>.hip
+// (minimum_time_problem(infeasible_problem(prob))).
+#define TOG_BUILTIN_MODELS(X)                        \
+  X(TOG_MODEL_DOUBLE_INTEGRATOR, double_integrator)  \
+  X(TOG_MODEL_CARTPOLE, cartpole)                    \
+  X(TOG_MODEL_QUADROTOR, quadrotor)                  \
+  X(TOG_MODEL_CAR, car)                              \
+  X(TOG_MODEL_PENDULUM, pendulum)                    \
+  X(TOG_MODEL_KUKA, kuka)
+
 namespace tog {
-const ModelOps* ops_double_integrator();
-const ModelOps* ops_cartpole();
-const ModelOps* ops_quadrotor();
-const ModelOps* ops_car();
-const ModelOps* ops_pendulum();
-const ModelOps* ops_kuka();
-const ModelOps* ops_kuka_implicit();
-// add_slack_controls(model) variants (infeasible start, src/model.jl:761-779)
-const ModelOps* ops_inf_double_integrator();
-const ModelOps* ops_inf_cartpole();
-const ModelOps* ops_inf_quadrotor();
-const ModelOps* ops_inf_car();
-const ModelOps* ops_inf_pendulum();
-const ModelOps* ops_inf_kuka();
-// add_min_time_controls(model) variants (minimum time, src/solvers/altro/minimum_time.jl:83-104)
-const ModelOps* ops_mt_pendulum();
-const ModelOps* ops_mtinf_pendulum();
-const ModelOps* ops_mtinf_car();
-const ModelOps* ops_mtinf_double_integrator();
-const ModelOps* ops_mtinf_cartpole();
-const ModelOps* ops_mtinf_quadrotor();
-const ModelOps* ops_mtinf_kuka();
-const ModelOps* ops_mt_car();
-const ModelOps* ops_mt_double_integrator();
-const ModelOps* ops_mt_quadrotor();
-const ModelOps* ops_mt_cartpole();
-const ModelOps* ops_mt_kuka();
+#define X(id, unit)                  \
+  const ModelOps* ops_##unit();      \
+  const ModelOps* ops_inf_##unit();  \
+  const ModelOps* ops_mt_##unit();   \
+  const ModelOps* ops_mtinf_##unit();
+TOG_BUILTIN_MODELS(X)
+#undef X
+const ModelOps* ops_kuka_implicit();  // the Kuka under the implicit integrators (k_kuka_implicit.hip)
 }  // namespace tog
 
 static thread_local std::string g_err;
@@ -124,7 +118,7 @@ struct tog_handle {
   std::vector<tog_handle*> parts;
   std::vector<long long> part_off;
   // second stream + fork/join events: the forward pass overlaps the decided trajectories' commit
-  // with the second speculative round (tog_kernels.hpp forward_i)
+  // with the second speculative round (tog_launch.hpp forward_i)
   StreamPair sp = {nullptr, nullptr, nullptr};
   // projected Newton workspace, allocated by the first tog_solve_pn (tog_pn.hpp)
   PNBuffers pn = {};
@@ -196,71 +190,34 @@ struct tog_model {
   const tog::ModelOps* ops_mt;  // MinTime<M> (add_min_time_controls)
 };
 
+// the built-in models' tables: at[variant: bit 0 infeasible, bit 1 minimum time][model id]
+struct BuiltinOps {
+  using fn = const ModelOps* (*)();
+  fn at[4][TOG_MODEL_COUNT];
+};
+static BuiltinOps builtin_ops() {
+  BuiltinOps t = {};
+#define X(id, unit)              \
+  t.at[0][id] = ops_##unit;      \
+  t.at[1][id] = ops_inf_##unit;  \
+  t.at[2][id] = ops_mt_##unit;   \
+  t.at[3][id] = ops_mtinf_##unit;
+  TOG_BUILTIN_MODELS(X)
+#undef X
+  return t;
+}
+
 static const ModelOps* ops_for(int model, bool infeasible, bool min_time, const tog_model* user, int integ) {
   if (model == TOG_MODEL_KUKA && !infeasible && !min_time && (integ == TOG_RK3_IMPLICIT || integ == TOG_MIDPOINT_IMPLICIT))
     return ops_kuka_implicit();
-  if (min_time && infeasible) {  // minimum_time_problem(infeasible_problem(prob))
-    switch (model) {
-      case TOG_MODEL_PENDULUM: return ops_mtinf_pendulum();
-      case TOG_MODEL_CAR: return ops_mtinf_car();
-      case TOG_MODEL_DOUBLE_INTEGRATOR: return ops_mtinf_double_integrator();
-      case TOG_MODEL_CARTPOLE: return ops_mtinf_cartpole();
-      case TOG_MODEL_QUADROTOR: return ops_mtinf_quadrotor();
-      case TOG_MODEL_KUKA: return ops_mtinf_kuka();
-    }
-    return nullptr;
+  if (model == TOG_MODEL_USER) {  // (a plugin has no minimum-time variant of its infeasible model)
+    if (!user || (min_time && infeasible)) return nullptr;
+    return min_time ? user->ops_mt : infeasible ? user->ops_inf : user->ops;
   }
-  if (min_time) {
-    if (model == TOG_MODEL_USER) return user ? user->ops_mt : nullptr;
-    switch (model) {
-      case TOG_MODEL_PENDULUM: return ops_mt_pendulum();
-      case TOG_MODEL_CAR: return ops_mt_car();
-      case TOG_MODEL_DOUBLE_INTEGRATOR: return ops_mt_double_integrator();
-      case TOG_MODEL_QUADROTOR: return ops_mt_quadrotor();
-      case TOG_MODEL_CARTPOLE: return ops_mt_cartpole();
-      case TOG_MODEL_KUKA: return ops_mt_kuka();
-    }
-    return nullptr;
-  }
-  if (model == TOG_MODEL_USER) return user ? (infeasible ? user->ops_inf : user->ops) : nullptr;
-  if (infeasible) {
-    switch (model) {
-      case TOG_MODEL_DOUBLE_INTEGRATOR: return ops_inf_double_integrator();
-      case TOG_MODEL_CARTPOLE: return ops_inf_cartpole();
-      case TOG_MODEL_QUADROTOR: return ops_inf_quadrotor();
-      case TOG_MODEL_CAR: return ops_inf_car();
-      case TOG_MODEL_PENDULUM: return ops_inf_pendulum();
-      case TOG_MODEL_KUKA: return ops_inf_kuka();
-    }
-    return nullptr;
-  }
-  switch (model) {
-    case TOG_MODEL_DOUBLE_INTEGRATOR: return ops_double_integrator();
-    case TOG_MODEL_CARTPOLE: return ops_cartpole();
-    case TOG_MODEL_QUADROTOR: return ops_quadrotor();
-    case TOG_MODEL_CAR: return ops_car();
-    case TOG_MODEL_PENDULUM: return ops_pendulum();
-    case TOG_MODEL_KUKA: return ops_kuka();
-  }
-  return nullptr;
-}
-
-// upper Cholesky (dpotrf 'U') of a symmetric matrix; returns false if not PD
-static bool host_chol_upper(const double* A, int n, double* U) {
-  for (int i = 0; i < n * n; i++) U[i] = 0.0;
-  for (int j = 0; j < n; j++) {
-    double s = A[j + n * j];
-    for (int k = 0; k < j; k++) s -= U[k + n * j] * U[k + n * j];
-    if (!(s > 0.0)) return false;
-    const double ujj = sqrt(s);
-    U[j + n * j] = ujj;
-    for (int c = j + 1; c < n; c++) {
-      double t = A[j + n * c];
-      for (int k = 0; k < j; k++) t -= U[k + n * j] * U[k + n * c];
-      U[j + n * c] = t / ujj;
-    }
-  }
-  return true;
+  if (model < 0 || model >= TOG_MODEL_COUNT) return nullptr;
+  static const BuiltinOps table = builtin_ops();
+  const BuiltinOps::fn f = table.at[(min_time ? 2 : 0) | (infeasible ? 1 : 0)][model];
+  return f ? f() : nullptr;
 }
 
 // Flatten the ordered constraint sets into per-knot rows (src/constraint_sets.jl:64-131).
@@ -874,131 +831,57 @@ int32_t tog_destroy(tog_handle* h) {
   return TOG_OK;
 }
 
-// Body of tog_create after argument validation: every early return (HIPCHECK, allocation, build_rows)
-// leaves the partially built handle to the caller, which destroys it (streams, events, allocations).
-static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog_options* opts,
-                             const ModelOps* ops, int32_t device) {
-  h->device = device;
-  HIPCHECK(hipSetDevice(device));
-  HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  h->own_stream = true;
-  HIPCHECK(hipStreamCreateWithFlags(&h->sp.st2, hipStreamNonBlocking));
-  HIPCHECK(hipEventCreateWithFlags(&h->sp.fork, hipEventDisableTiming));
-  HIPCHECK(hipEventCreateWithFlags(&h->sp.join, hipEventDisableTiming));
-  h->model = d->model;
-  h->integ = d->integrator;
-  h->n = d->n;
-  h->m = d->m;
-  h->N = d->N;
-  h->B = d->batch;
-  h->opts = *opts;
-  h->ops = ops;
-  const int n = h->n, m = h->m, N = h->N;
-  h->nq = n + m + n * n + m * m + m * n;
+// tog_create after argument validation, in parts (create_single below runs them in order). Every early return
+// (HIPCHECK, allocation, build_rows) leaves the partially built handle to the caller, which destroys it (streams,
+// events, allocations).
 
+// the descriptor's constraint sets as per-knot rows (build_rows)
+struct HostRows {
   std::vector<ConRow> rows;
-  std::vector<int> off, cnt;
-  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, rows, off, cnt);
-  if (rc) return rc;
-  h->nrows = (int)rows.size();
-  h->pmax = 0;
-  for (int k = 0; k < N; k++) h->pmax = cnt[k] > h->pmax ? cnt[k] : h->pmax;
+  std::vector<int> off, cnt;  // first row and row count of each knot
+  // rows with a state gradient per knot (every row type but the control bounds): the knots whose
+  // square-root expansion changes Q.xx (expansion records, tog_bwd_team.hpp ne_of)
+  std::vector<int> nx;
+};
 
+// 1. h->hostP from the descriptor, the rows and the host plan (tog_host_plan.hpp); no device work
+static int32_t fill_problem(tog_handle* h, const tog_problem_desc* d, const tog_options* opts, const HostRows& hr,
+                            const tog_plan::CostPlan& cp) {
+  const int n = h->n, m = h->m;
   DevProblem& P = h->hostP;
   memset(&P, 0, sizeof(P));
   P.n = n;
   P.m = m;
-  P.N = N;
+  P.N = h->N;
   P.pmax = h->pmax;
   P.model = d->model;
   P.integ = d->integrator;
   P.nrows = h->nrows;
   P.B = h->B;
   P.dt = d->dt;
-  // the stage cost(s): one for every knot, or a time-varying Objective's table (desc->stage_costs, rows
-  // [Q; R; H; q; r; c]); the device table adds each knot's square-root factors cQ, cR (DevProblem::kc)
-  const int nc_in = n * n + m * m + m * n + n + m + 1, kst = 2 * n * n + 2 * m * m + m * n + n + m + 1;
-  const int nk = d->stage_costs ? N - 1 : 1;
-  std::vector<double> kc((size_t)nk * kst, 0.0);
-  for (int k = 0; k < nk; k++) {
-    double* o = kc.data() + (size_t)k * kst;
-    if (d->stage_costs) {
-      memcpy(o, d->stage_costs + (size_t)k * nc_in, sizeof(double) * nc_in);
-    } else {
-      memcpy(o, d->Q, sizeof(double) * n * n);
-      memcpy(o + n * n, d->R, sizeof(double) * m * m);
-      memcpy(o + n * n + m * m, d->H, sizeof(double) * m * n);
-      memcpy(o + n * n + m * m + m * n, d->q, sizeof(double) * n);
-      memcpy(o + n * n + m * m + m * n + n, d->r, sizeof(double) * m);
-      o[nc_in - 1] = d->c;
-    }
-  }
-  auto kQ = [&](int k) { return kc.data() + (size_t)k * kst; };
-  auto kR = [&](int k) { return kQ(k) + n * n; };
-  auto kH = [&](int k) { return kR(k) + m * m; };
-  auto kcQ = [&](int k) { return kQ(k) + nc_in; };
-  auto kcR = [&](int k) { return kcQ(k) + n * n; };
   // P's own cost fields hold knot 0's (the shared one without a table)
-  memcpy(P.Q, kQ(0), sizeof(double) * n * n);
-  memcpy(P.R, kR(0), sizeof(double) * m * m);
-  memcpy(P.H, kH(0), sizeof(double) * m * n);
-  memcpy(P.q, kH(0) + m * n, sizeof(double) * n);
-  memcpy(P.r, kH(0) + m * n + n, sizeof(double) * m);
-  P.c = kQ(0)[nc_in - 1];
+  memcpy(P.Q, cp.Q(0), sizeof(double) * n * n);
+  memcpy(P.R, cp.R(0), sizeof(double) * m * m);
+  memcpy(P.H, cp.H(0), sizeof(double) * m * n);
+  memcpy(P.q, cp.q(0), sizeof(double) * n);
+  memcpy(P.r, cp.r(0), sizeof(double) * m);
+  P.c = cp.c(0);
   memcpy(P.Qf, d->Qf, sizeof(double) * n * n);
   memcpy(P.qf, d->qf, sizeof(double) * n);
   P.cf = d->cf;
-  {
-    bool ok = host_chol_upper(P.Qf, n, P.cQf);
-    for (int k = 0; k < nk; k++) {
-      double Qdt[NMAX * NMAX], Rdt[MMAX * MMAX];
-      for (int i = 0; i < n * n; i++) Qdt[i] = kQ(k)[i] * P.dt;
-      for (int i = 0; i < m * m; i++) Rdt[i] = kR(k)[i] * P.dt;
-      ok = host_chol_upper(Qdt, n, kcQ(k)) && host_chol_upper(Rdt, m, kcR(k)) && ok;
-    }
-    memcpy(P.cQ, kcQ(0), sizeof(double) * n * n);
-    memcpy(P.cR, kcR(0), sizeof(double) * m * m);
-    P.sqrt_ok = ok ? 1 : 0;
-    bool diag = true;
-    for (int j = 0; j < n; j++)
-      for (int i = 0; i < n; i++)
-        if (i != j && P.Qf[i + n * j] != 0.0) diag = false;
-    for (int k = 0; k < nk; k++) {
-      for (int j = 0; j < n; j++)
-        for (int i = 0; i < n; i++)
-          if (i != j && kQ(k)[i + n * j] != 0.0) diag = false;
-      for (int j = 0; j < m; j++)
-        for (int i = 0; i < m; i++)
-          if (i != j && kR(k)[i + m * j] != 0.0) diag = false;
-      for (int i = 0; i < m * n; i++)
-        if (kH(k)[i] != 0.0) diag = false;
-    }
-    // 2: diagonal with every off-diagonal entry (and H, and the factors' off-diagonals) +0.0 and
-    // dt > 0, so the kernels may use literal zeros for them and stay bit-identical
-    bool pz = diag && P.dt > 0.0;
-    auto offdiag_pz = [&](const double* A, int kk) {
-      for (int j = 0; j < kk; j++)
-        for (int i = 0; i < kk; i++)
-          if (i != j && (A[i + kk * j] != 0.0 || std::signbit(A[i + kk * j]))) return false;
-      return true;
-    };
-    if (pz) pz = offdiag_pz(P.Qf, n) && (!ok || offdiag_pz(P.cQf, n));
-    for (int k = 0; pz && k < nk; k++) {
-      pz = offdiag_pz(kQ(k), n) && offdiag_pz(kR(k), m);
-      if (pz && ok) pz = offdiag_pz(kcQ(k), n) && offdiag_pz(kcR(k), m);
-      for (int i = 0; pz && i < m * n; i++)
-        if (std::signbit(kH(k)[i])) pz = false;
-    }
-    P.diag_cost = diag ? (pz ? 2 : 1) : 0;
-    h->buf.cost_diag = P.diag_cost;
-    if (opts->square_root && !ok) {
-      return fail(TOG_ERR_ARG, "cost Hessians must be PD for the sqrt backward pass (objective.jl:70-94)");
-    }
-  }
+  memcpy(P.cQf, cp.cQf.data(), sizeof(double) * n * n);
+  memcpy(P.cQ, cp.cQ(0), sizeof(double) * n * n);
+  memcpy(P.cR, cp.cR(0), sizeof(double) * m * m);
+  P.sqrt_ok = cp.sqrt_ok ? 1 : 0;
+  P.diag_cost = cp.diag_cost;
+  h->buf.cost_diag = P.diag_cost;
+  if (opts->square_root && !cp.sqrt_ok)
+    return fail(TOG_ERR_ARG, "cost Hessians must be PD for the sqrt backward pass (objective.jl:70-94)");
   // packed std AL expansion records: the Q.xx entries a stage row can change (row_grad's state indices)
   {
-    unsigned int pat[NMAX] = {0};
-    for (const ConRow& r : rows) {
+    std::vector<unsigned int> masks;
+    masks.reserve(hr.rows.size());
+    for (const ConRow& r : hr.rows) {
       unsigned int sx = 0;
       switch (r.type) {
         case ROW_XMAX: case ROW_XMIN: case ROW_GOAL: case ROW_MT_EQ: sx = 1u << r.idx; break;
@@ -1007,100 +890,131 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
         case ROW_SPHERE: sx = 7u; break;
         default: sx = (1u << n) - 1u;  // user rows: dense
       }
-      for (int c = 0; c < n; c++)
-        if (sx >> c & 1u) pat[c] |= sx;
+      masks.push_back(sx);
     }
-    int off = 0;
-    P.qpat_max = 0;
+    const tog_plan::QPattern qp = tog_plan::plan_qpattern(n, masks.data(), masks.size());
     for (int c = 0; c < n; c++) {
-      P.qpat[c] = pat[c];
-      P.qoff[c] = off;
-      off += __builtin_popcount(pat[c]);
-      P.qpat_max = std::max(P.qpat_max, __builtin_popcount(pat[c]));
+      P.qpat[c] = qp.qpat[c];
+      P.qoff[c] = qp.qoff[c];
     }
-    P.qpat_n = off;
+    P.qpat_n = qp.qpat_n;
+    P.qpat_max = qp.qpat_max;
     // (the expansion's pattern loop: every column within QPK pattern rows; TOG_DENSE_RECORDS=1 runs the
     // general loop, for A/B checks)
     P.qpat_on = (P.qpat_max <= QPK && getenv("TOG_DENSE_RECORDS") == nullptr) ? 1 : 0;
   }
   P.kc = nullptr;
-  P.kc_stride = kst;
+  P.kc_stride = cp.kst;
   P.kc_pad = 0;
-  if (d->stage_costs) {
-    double* dkc = nullptr;
-    if ((rc = dalloc(h, &dkc, kc.size()))) return rc;
-    HIPCHECK(hipMemcpy(dkc, kc.data(), sizeof(double) * kc.size(), hipMemcpyHostToDevice));
-    P.kc = dkc;
-  } else {
-    h->kc_row = kc;  // (one row: replicated per knot when per-trajectory data is set, traj_apply)
-  }
-  h->kc0 = P.kc;
   {
-    std::vector<int> rt(rows.size()), ri(rows.size());
-    for (size_t i = 0; i < rows.size(); i++) {
-      rt[i] = rows[i].type;
-      ri[i] = rows[i].idx;
+    std::vector<int> rt(hr.rows.size()), ri(hr.rows.size());
+    for (size_t i = 0; i < hr.rows.size(); i++) {
+      rt[i] = hr.rows[i].type;
+      ri[i] = hr.rows[i].idx;
     }
-    h->goal_err = tog_traj::terminal_goal_rows(rt.data(), ri.data(), off.data(), cnt.data(), N, n, ROW_GOAL, h->goal_idx);
+    h->goal_err =
+        tog_traj::terminal_goal_rows(rt.data(), ri.data(), hr.off.data(), hr.cnt.data(), h->N, n, ROW_GOAL, h->goal_idx);
   }
   P.o = *opts;
   P.R_min_time = (d->flags & TOG_PROB_MIN_TIME) ? d->R_min_time : 0.0;
-  const size_t B = (size_t)h->B, P1 = (size_t)(h->pmax > 0 ? h->pmax : 1);
-  // rows with a state gradient per knot (every row type but the control bounds): the knots whose
-  // square-root expansion changes Q.xx (expansion records, tog_bwd_team.hpp ne_of)
-  std::vector<int> nxk(N, 0);
-  for (int k = 0; k < N; k++)
-    for (int r = 0; r < cnt[k]; r++) {
-      const int t = rows[off[k] + r].type;
-      if (t != ROW_UMAX && t != ROW_UMIN) nxk[k]++;
-    }
+  return TOG_OK;
+}
+
+// 2. the device tables hostP points to (a time-varying Objective's cost table, the constraint rows), then hostP
+// itself
+static int32_t upload_tables(tog_handle* h, const tog_problem_desc* d, const HostRows& hr,
+                             const tog_plan::CostPlan& cp) {
+  int rc;
+  const int N = h->N;
+  DevProblem& P = h->hostP;
+  if (d->stage_costs) {
+    double* dkc = nullptr;
+    if ((rc = dalloc(h, &dkc, cp.kc.size()))) return rc;
+    HIPCHECK(hipMemcpy(dkc, cp.kc.data(), sizeof(double) * cp.kc.size(), hipMemcpyHostToDevice));
+    P.kc = dkc;
+  } else {
+    h->kc_row = cp.kc;  // (one row: replicated per knot when per-trajectory data is set, traj_apply)
+  }
+  h->kc0 = P.kc;
   if ((rc = dalloc(h, &h->d_knot_off, N)) || (rc = dalloc(h, &h->d_knot_cnt, N)) ||
-      (rc = dalloc(h, &h->d_knot_nx, N)) || (rc = dalloc(h, &h->d_rows, rows.size() + 1)) ||
+      (rc = dalloc(h, &h->d_knot_nx, N)) || (rc = dalloc(h, &h->d_rows, hr.rows.size() + 1)) ||
       (rc = dalloc(h, &h->dP, 1)))
     return rc;
-  HIPCHECK(hipMemcpy(h->d_knot_off, off.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(h->d_knot_cnt, cnt.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(h->d_knot_nx, nxk.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-  if (!rows.empty()) HIPCHECK(hipMemcpy(h->d_rows, rows.data(), sizeof(ConRow) * rows.size(), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h->d_knot_off, hr.off.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h->d_knot_cnt, hr.cnt.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h->d_knot_nx, hr.nx.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+  if (!hr.rows.empty())
+    HIPCHECK(hipMemcpy(h->d_rows, hr.rows.data(), sizeof(ConRow) * hr.rows.size(), hipMemcpyHostToDevice));
+  P.knot_off = h->d_knot_off;
+  P.knot_cnt = h->d_knot_cnt;
+  P.knot_nx = h->d_knot_nx;
+  P.rows = h->d_rows;
+  HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
+  return TOG_OK;
+}
+
+// 3. the kernel variants of this problem (h->bwd_team and the launch fields of h->buf); returns whether the line
+// search is the candidate-copy one
+static bool choose_variants(tog_handle* h, const tog_problem_desc* d, const tog_options* opts, const HostRows& hr) {
+  const int n = h->n, m = h->m, N = h->N, nrows = (int)hr.rows.size();
+  const ModelOps* ops = h->ops;
+  DevBuffers& b = h->buf;
   {
     // TOG_BWD=lds forces the one-wave-per-trajectory LDS backward kernel (A/B checks)
     const char* ev = getenv("TOG_BWD");
     const bool force_lds = ev && strcmp(ev, "lds") == 0;
     // (a time-varying Objective runs the team kernels' TV variants, which read knot k's cost from the table)
     h->bwd_team = (!force_lds && !ops->min_time &&
-                   team_rows_fit(off.data(), cnt.data(), rows.data(), N, n, m, (int)rows.size()))
+                   team_rows_fit(hr.off.data(), hr.cnt.data(), hr.rows.data(), N, n, m, nrows))
                       ? 1 : 0;
     for (int sq = 0; sq < 2; sq++) {
-      h->buf.bwd_stride2[sq] = ops->team_stride(h->pmax, sq);
-      h->buf.bwd_shmem2[sq] = (int)bwd_team_shmem(h->buf.bwd_stride2[sq], ops->team_tpw, (int)rows.size(), N);
-      if (h->buf.bwd_shmem2[sq] > 64 * 1024) h->bwd_team = 0;
+      b.bwd_stride2[sq] = ops->team_stride(h->pmax, sq);
+      b.bwd_shmem2[sq] = (int)bwd_team_shmem(b.bwd_stride2[sq], ops->team_tpw, nrows, N);
+      if (b.bwd_shmem2[sq] > 64 * 1024) h->bwd_team = 0;
     }
   }
-  // bulk k_ls_spec: a block's LDS copy of the row tables (TOG_SPEC_RT=global: the constant-space reads)
-  h->buf.rows_lds = getenv("TOG_SPEC_RT") && strcmp(getenv("TOG_SPEC_RT"), "global") == 0
-                        ? 0
-                        : row_tables_bytes((int)rows.size(), N);
-  // k_ls_spec_tail (tail rollouts staged through LDS): admissible up to SPEC_TAIL_PMAX rows per knot
-  {  // k_ls_spec_tail2 (two waves): within 64 KB of LDS; TOG_NO_SPEC_TAIL2 keeps the one-wave kernel
+  // bulk k_ls_spec: a block's LDS copy of the row tables
+  b.rows_lds = row_tables_bytes(nrows, N);
+  // the tail rollouts staged through LDS, admissible up to SPEC_TAIL_PMAX rows per knot: k_ls_spec_tail2 (two
+  // waves) within 64 KB of LDS, else the one-wave k_ls_spec_tail
+  {
     const size_t b2 = sizeof(double) * (size_t)spec_tail2_doubles(n, m, h->pmax);
-    h->buf.spec_tail2_shmem =
-        (h->pmax <= SPEC_TAIL_PMAX && b2 <= 64 * 1024 && !getenv("TOG_NO_SPEC_TAIL2")) ? (int)b2 : 0;
+    b.spec_tail2_shmem = (h->pmax <= SPEC_TAIL_PMAX && b2 <= 64 * 1024) ? (int)b2 : 0;
   }
-  h->buf.spec_tail_shmem = (h->pmax <= SPEC_TAIL_PMAX && !getenv("TOG_NO_SPEC_TAIL"))
-                               ? (int)(sizeof(double) * (spec_tail_tc(n, m) * spec_tail_rec(n, m, h->pmax) + 2 * h->pmax))
-                               : 0;
-  P.knot_off = h->d_knot_off;
-  P.knot_cnt = h->d_knot_cnt;
-  P.knot_nx = h->d_knot_nx;
-  P.rows = h->d_rows;
-  HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
-
-  DevBuffers& b = h->buf;
+  b.spec_tail_shmem = h->pmax <= SPEC_TAIL_PMAX
+                          ? (int)(sizeof(double) * (spec_tail_tc(n, m) * spec_tail_rec(n, m, h->pmax) + 2 * h->pmax))
+                          : 0;
   b.tv = d->stage_costs ? 1 : 0;
   h->tv0 = b.tv;
   b.dense_stage_knots = 0;  // a stage knot with a state row (its square-root expansion changes Q.xx)
   for (int k = 0; k + 1 < N; k++)
-    if (nxk[k] > 0) b.dense_stage_knots = 1;
+    if (hr.nx[k] > 0) b.dense_stage_knots = 1;
+  b.nc = opts->iterations_linesearch + 1 < 64 ? opts->iterations_linesearch + 1 : 64;
+  if (b.nc < 1) b.nc = 1;
+  b.ncp = (b.nc + 7) & ~7;
+  b.nknots = N;
+  b.tail = 0;
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 0;
+    b.simds = 4 * cus;
+  }
+  b.ls_pend_ok = getenv("TOG_LS_NOPEND") ? 0 : 1;
+  b.ls_first = LS_FIRST;
+  // candidate-copy line search when every trial fits the speculative window (TOG_LS=replay: the
+  // replaying k_ls_commit path, for A/B checks)
+  const char* ev = getenv("TOG_LS");
+  const bool replay = ev && strcmp(ev, "replay") == 0;
+  return !replay && opts->iterations_linesearch + 1 <= 64;
+}
+
+// 4. every per-trajectory device buffer of the handle
+static int32_t allocate(tog_handle* h, const tog_problem_desc* d, bool cand_ls) {
+  int rc;
+  const size_t B = (size_t)h->B, n = (size_t)h->n, m = (size_t)h->m, N = (size_t)h->N;
+  const size_t P1 = (size_t)(h->pmax > 0 ? h->pmax : 1);
+  const ModelOps* ops = h->ops;
+  DevBuffers& b = h->buf;
   if ((rc = dalloc(h, &b.x0, B * n)) || (rc = dalloc(h, &b.X, B * N * n)) || (rc = dalloc(h, &b.U, B * (N - 1) * m)) ||
       (rc = dalloc(h, &b.Xb, B * N * n)) || (rc = dalloc(h, &b.Ub, B * (N - 1) * m)) ||
       (rc = dalloc(h, &b.AB, B * (N - 1) * n * (n + m))) || (rc = dalloc(h, &b.K, B * (N - 1) * m * n)) ||
@@ -1125,43 +1039,33 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
   b.hcap = 0;
   b.ocap = 0;
   if (h->bwd_team) {  // expansion records of the team backward pass (k_expand_team)
-    const size_t ne = (size_t)n + m + (size_t)m * m + (size_t)n * n;
+    const size_t ne = n + m + m * m + n * n;
     if ((rc = dalloc(h, &b.E, B * N * ne))) return rc;
   }
-  b.nc = opts->iterations_linesearch + 1 < 64 ? opts->iterations_linesearch + 1 : 64;
-  if (b.nc < 1) b.nc = 1;
-  b.nknots = N;
   b.jws = nullptr;
-  b.jac_chain = (getenv("TOG_KUKA_JAC") && strcmp(getenv("TOG_KUKA_JAC"), "dual") == 0) ? 0 : 1;
-  // staged RK3 Jacobian (the RBD model): the stage state of every (knot, partial) lane
-  if (ops->jws_per_lane > 0 && d->integrator == TOG_RK3 && !getenv("TOG_JAC_UNSTAGED")) {
-    const size_t lanes = B * (size_t)(N - 1) * (size_t)(ops->n + ops->m - ops->slack);
+  // the RBD model's RK3 Jacobian in stage-chain form (tog_kuka_jac.hpp): KJ_WSK doubles per (trajectory, knot).
+  // (The allocation keeps the size of the form it replaced, jws_per_lane doubles for each of a knot's n + m
+  // partials, which is the larger.)
+  if (ops->jws_per_lane > 0 && d->integrator == TOG_RK3) {
+    const size_t lanes = B * (N - 1) * (size_t)(ops->n + ops->m - ops->slack);
     if ((rc = dalloc(h, &b.jws, lanes * (size_t)ops->jws_per_lane))) return rc;
   }
-  b.ncp = (b.nc + 7) & ~7;
-  b.tail = 0;
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 0;
-    b.simds = getenv("TOG_BWD_W2") ? 0 : 4 * cus;  // (TOG_BWD_W2: the 2-wave variant at every batch size, A/B)
-  }
-  b.ls_pend_ok = getenv("TOG_LS_NOPEND") ? 0 : 1;
-  b.ls_first = LS_FIRST;
   b.cand = nullptr;
   b.ls_fb = nullptr;
-  // candidate-copy line search when every trial fits the speculative window (TOG_LS=replay: the
-  // replaying k_ls_commit path, for A/B checks)
-  {
-    const char* ev = getenv("TOG_LS");
-    const bool replay = ev && strcmp(ev, "replay") == 0;
-    if (!replay && opts->iterations_linesearch + 1 <= 64) {
-      if ((rc = dalloc(h, &b.cand, B * (size_t)b.ncp * N * 4 * ((n + m + 3) / 4))) || (rc = dalloc(h, &b.ls_win, B)) ||
-          (rc = dalloc(h, &b.ls_Jw, B)) || (rc = dalloc(h, &b.gk, B * N)) || (rc = dalloc(h, &b.ls_fb, B)))
-        return rc;
-    }
+  if (cand_ls) {
+    if ((rc = dalloc(h, &b.cand, B * (size_t)b.ncp * N * 4 * ((n + m + 3) / 4))) || (rc = dalloc(h, &b.ls_win, B)) ||
+        (rc = dalloc(h, &b.ls_Jw, B)) || (rc = dalloc(h, &b.gk, B * N)) || (rc = dalloc(h, &b.ls_fb, B)))
+      return rc;
   }
-  // reference constructor state: X = NaN, U = 0, K = d = 0, λ = 0, μ = opts.penalty_initial,
-  // ρ = dρ = 0 (ilqr_solver.jl:118-144, augmented_lagrangian_solver.jl:143-169)
+  return TOG_OK;
+}
+
+// 5. reference constructor state: X = NaN, U = 0, K = d = 0, λ = 0, μ = opts.penalty_initial,
+// ρ = dρ = 0 (ilqr_solver.jl:118-144, augmented_lagrangian_solver.jl:143-169)
+static int32_t reset_state(tog_handle* h) {
+  const size_t B = (size_t)h->B, n = (size_t)h->n, m = (size_t)h->m, N = (size_t)h->N;
+  const size_t P1 = (size_t)(h->pmax > 0 ? h->pmax : 1);
+  DevBuffers& b = h->buf;
   fill(h, b.x0, B * n, 0.0);
   fill(h, b.X, B * N * n, NAN);
   fill(h, b.U, B * (N - 1) * m, 0.0);
@@ -1177,6 +1081,49 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TOG_OK;
+}
+
+static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog_options* opts,
+                             const ModelOps* ops, int32_t device) {
+  h->device = device;
+  HIPCHECK(hipSetDevice(device));
+  HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  h->own_stream = true;
+  HIPCHECK(hipStreamCreateWithFlags(&h->sp.st2, hipStreamNonBlocking));
+  HIPCHECK(hipEventCreateWithFlags(&h->sp.fork, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&h->sp.join, hipEventDisableTiming));
+  h->model = d->model;
+  h->integ = d->integrator;
+  h->n = d->n;
+  h->m = d->m;
+  h->N = d->N;
+  h->B = d->batch;
+  h->opts = *opts;
+  h->ops = ops;
+  const int n = h->n, m = h->m, N = h->N;
+  h->nq = n + m + n * n + m * m + m * n;
+
+  HostRows hr;
+  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, hr.rows, hr.off, hr.cnt);
+  if (rc) return rc;
+  h->nrows = (int)hr.rows.size();
+  h->pmax = 0;
+  hr.nx.assign(N, 0);
+  for (int k = 0; k < N; k++) {
+    h->pmax = hr.cnt[k] > h->pmax ? hr.cnt[k] : h->pmax;
+    for (int r = 0; r < hr.cnt[k]; r++) {
+      const int t = hr.rows[hr.off[k] + r].type;
+      if (t != ROW_UMAX && t != ROW_UMIN) hr.nx[k]++;
+    }
+  }
+  // the stage cost(s): one for every knot, or a time-varying Objective's table (desc->stage_costs, rows
+  // [Q; R; H; q; r; c]); the device table adds each knot's square-root factors cQ, cR (DevProblem::kc)
+  const tog_plan::CostPlan cp =
+      tog_plan::plan_costs(n, m, N, d->dt, d->Q, d->R, d->H, d->q, d->r, d->c, d->stage_costs, d->Qf);
+  if ((rc = fill_problem(h, d, opts, hr, cp)) || (rc = upload_tables(h, d, hr, cp))) return rc;
+  const bool cand_ls = choose_variants(h, d, opts, hr);
+  if ((rc = allocate(h, d, cand_ls))) return rc;
+  return reset_state(h);
 }
 
 int32_t tog_create(const tog_problem_desc* d, const tog_options* opts, int32_t device, tog_handle** out) {
@@ -1305,15 +1252,18 @@ int32_t tog_history_enable(tog_handle* h, int32_t capacity) {
     b.hcap = b.ocap = 0;
     return TOG_OK;
   }
-  if (capacity > h->hist_cap_alloc || ocap > h->hist_ocap_alloc || !h->hist_in_alloc) {  // grow (old ones released)
-    int rc;
-    dfree(h, h->hist_in_alloc);
-    dfree(h, h->hist_out_alloc);
-    h->hist_in_alloc = h->hist_out_alloc = nullptr;
-    h->hist_cap_alloc = h->hist_ocap_alloc = 0;
-    if ((rc = dalloc(h, &h->hist_in_alloc, (size_t)h->B * 3 * capacity)) ||
-        (rc = dalloc(h, &h->hist_out_alloc, (size_t)h->B * 4 * ocap)))
-      return rc;
+  if (capacity > h->hist_cap_alloc || ocap > h->hist_ocap_alloc || !h->hist_in_alloc) {
+    // grow: both new buffers before the old ones go, so a failed allocation leaves the handle as it was
+    int rc = TOG_OK;
+    const bool ok = tog_traj::replace_buffer_pair(
+        &h->hist_in_alloc, (size_t)h->B * 3 * capacity, &h->hist_out_alloc, (size_t)h->B * 4 * ocap,
+        [&](size_t c) {
+          double* p = nullptr;
+          rc = dalloc(h, &p, c);
+          return rc == TOG_OK ? p : nullptr;
+        },
+        [&](double* p) { dfree(h, p); });
+    if (!ok) return rc;
     h->hist_cap_alloc = capacity;
     h->hist_ocap_alloc = ocap;
   }
@@ -1803,10 +1753,7 @@ int32_t tog_solve_step(tog_handle* h, int32_t nsteps) {
     timed(h, TOG_KERNEL_BACKWARD,
           [&] { h->ops->backward(h->dP, Bt, Bl, h->opts.square_root, al, 0, h->bwd_team, h->stream); });
     timed(h, TOG_KERNEL_FORWARD,
-          [&] {
-            h->ops->forward(h->dP, Bt, Bl, h->integ, h->mode, 1, nullptr, nullptr, h->stream,
-                            getenv("TOG_NO_OVERLAP") ? nullptr : &h->sp);
-          });
+          [&] { h->ops->forward(h->dP, Bt, Bl, h->integ, h->mode, 1, nullptr, nullptr, h->stream, &h->sp); });
   }
   HIPCHECK(hipGetLastError());
   return TOG_OK;

@@ -1,6 +1,6 @@
 // Host side of the per-trajectory cost and goal tables (tog_set_trajectory_costs / tog_set_trajectory_goals,
 // include/tog.h): argument checks, the host images of the device tables, the slices a multi-device handle hands
-// to its parts, and the replace order of a device buffer. Plain C++ with no device runtime in it, so that a
+// to its parts, and the replace order of a device buffer (and of tog_history_enable's pair). Plain C++ with no device runtime in it, so that a
 // stand-alone program can run it under the host sanitizers (tests/c/traj_tables_host.cpp).
 #pragma once
 #include <cstddef>
@@ -75,6 +75,26 @@ inline bool replace_buffer(double** slot, const double* src, size_t count, Alloc
   double* old = *slot;
   *slot = fresh;
   if (old) release(old);
+  return true;
+}
+// Replace two device buffers together by fresh ones of count_a and count_b doubles (contents undefined; the
+// iteration histories of tog_history_enable). Both are allocated first: if either allocation fails, whatever was
+// freshly allocated is released, both slots and the old buffers stay untouched, and it returns false. Otherwise
+// the old ones are released and the slots updated.
+template <class Alloc, class Release>
+inline bool replace_buffer_pair(double** slot_a, size_t count_a, double** slot_b, size_t count_b, Alloc&& alloc,
+                                Release&& release) {
+  double* a = alloc(count_a);
+  if (!a) return false;
+  double* b = alloc(count_b);
+  if (!b) {
+    release(a);
+    return false;
+  }
+  if (*slot_a) release(*slot_a);
+  if (*slot_b) release(*slot_b);
+  *slot_a = a;
+  *slot_b = b;
   return true;
 }
 // back to the shared values: release the table (null: nothing)
