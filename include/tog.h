@@ -35,6 +35,8 @@ extern "C" {
       tog_problem_desc.stage_costs (time-varying objectives) */
 /* 5: per-trajectory linear cost terms and goals within one batch (tog_set_trajectory_costs,
       tog_set_trajectory_goals) */
+/* still 5: the streamed solves (tog_finished, tog_get_slots, tog_refill, tog_refill_tables, tog_solve_stream,
+      tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed */
 #define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
@@ -463,6 +465,46 @@ int32_t tog_solve(tog_handle* h, int32_t mode, int32_t max_steps);
 int32_t tog_solve_budget(tog_handle* h, int32_t mode);
 /* per-trajectory tog_traj_flag bits; flags_out: (B) int32 */
 int32_t tog_status(tog_handle* h, int32_t* flags_out);
+
+/* ---- streamed solves: J jobs through the handle's B trajectory slots ----
+   A slot whose trajectory finished is harvested and given the next job while the other slots keep iterating, so a
+   sweep of more starts than fit one batch does not pay the convergence tail once per batch. A job's result does not
+   depend on the slot, the step or the launch widths that served it: it is bit for bit what the same job gives in a
+   plain batch. The step-level pieces are exported for a caller's own loop; tog_solve_stream is the driver over them.
+   Single-device handles only (TOG_ERR_UNSUPPORTED on a tog_create_multi handle: stream one handle per device).
+   Refills happen between tog_solve_step calls, and a tog_batch_stats_begin is ended before a refill. */
+/* slots whose trajectory has finished and has not been listed before (after tog_solve_init every slot holds one;
+   a listed slot counts as harvested and is listed again only after a tog_refill): slots_out (B) int32, ascending;
+   count_out. Blocking. */
+int32_t tog_finished(tog_handle* h, int32_t* slots_out, int32_t* count_out);
+/* tog_get for listed slots only: out is (field block, count) in list order; marks nothing. Every field of tog_get
+   but TOG_FIELD_A / _B. Blocking. */
+int32_t tog_get_slots(tog_handle* h, int32_t field, int32_t count, const int32_t* slots, double* out);
+/* start new trajectories in inactive slots, in the mode of the last tog_solve_init: x0 (n,count), U (m,N-1,count),
+   X (n,N,count) or NULL (NaN: the initial rollout). Leaves each slot as tog_set_state + tog_solve_init would, bit
+   for bit, with the slot's d zeroed. TOG_ERR_ARG if a listed slot is active or listed twice. */
+int32_t tog_refill(tog_handle* h, int32_t count, const int32_t* slots, const double* x0, const double* U, const double* X);
+/* the listed slots' rows of the per-trajectory tables, before their tog_refill: lin (n+m+1,count) or
+   (n+m+1,N-1,count) as the handle's table is laid out, term (n+1,count), xf (ng,count); each may be NULL.
+   TOG_ERR_UNSUPPORTED for a table the handle does not have (tog_set_trajectory_costs / _goals set them first: the
+   kernel variants are chosen then). */
+int32_t tog_refill_tables(tog_handle* h, int32_t count, const int32_t* slots, const double* lin, const double* term,
+                          const double* xf);
+/* J jobs through the handle's B slots (J may be below B: the other slots stay empty and inactive); mode
+   TOG_MODE_ILQR or TOG_MODE_AL. x0 (n,J), U0 (m,N-1,J). Outputs indexed by job: X_out (n,N,J), U_out (m,N-1,J),
+   stats_out (TOG_NSTATS,J); any may be NULL. max_steps <= 0: no batch-step bound other than every job's own
+   iteration limits. When max_steps expires, unfinished jobs are returned as they stand with TOG_TRAJ_ACTIVE set,
+   jobs never started get a zero stats row (their X_out, U_out rows are not written); jobs_done (may be NULL) is
+   the number that finished. Iteration histories are not among the outputs (tog_get_slots serves them to a
+   caller's own loop). Blocking. TOG_ERR_ARG on a handle with per-trajectory tables (use the _tables entry). */
+int32_t tog_solve_stream(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0,
+                         double* X_out, double* U_out, double* stats_out, int32_t max_steps, int64_t* jobs_done);
+/* tog_solve_stream with per-job rows of the handle's per-trajectory tables (a goal sweep): lin, term, xf as in
+   tog_refill_tables with J columns; every table the handle has must be given, and none it has not
+   (TOG_ERR_UNSUPPORTED, also on a handle without tables). */
+int32_t tog_solve_stream_tables(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0,
+                                const double* lin, const double* term, const double* xf, double* X_out,
+                                double* U_out, double* stats_out, int32_t max_steps, int64_t* jobs_done);
 
 /* ---- ALTRO phase 2: projected Newton (src/solvers/direct/projected_newton.jl) ---- */
 /* ProjectedNewtonSolverOptions (src/solvers/direct/direct_solvers.jl:14-30); tog_default_pn_options

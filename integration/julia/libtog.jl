@@ -490,6 +490,79 @@ function tog_set_trajectory_goals!(s::BatchediLQRSolver, xf::Union{Nothing,Matri
     return nothing
 end
 
+"""
+    tog_finished(solver) -> Vector{Int32}
+    tog_get_slots(solver, field, slots, width) -> Matrix{Float64}   # width: the field's doubles per trajectory
+    tog_refill!(solver, slots, x0, U, X = nothing)
+    tog_refill_tables!(solver, slots, lin, term, xf)
+    tog_solve_stream!(solver, mode, x0, U0; lin, term, xf, max_steps) -> (X, U, stats, jobs_done)
+
+Streamed solves (include/tog.h): `J` jobs through the solver's `B` trajectory slots; a slot whose trajectory
+finished takes the next job while the others keep iterating. Slots are 0-based, as in the C ABI. The arrays carry
+the job (or listed slot) on the last axis: `x0 (n, J)`, `U0 (m, N-1, J)`, outputs `X (n, N, J)`, `U (m, N-1, J)`,
+`stats (TOG_NSTATS, J)`. `tog_solve_stream!` with any of `lin`, `term`, `xf` (columns per job, as
+`tog_set_trajectory_costs!` / `tog_set_trajectory_goals!` take them per trajectory) calls `tog_solve_stream_tables`,
+which needs those tables set on the solver beforehand. The ABI version stays 5: these are new functions only.
+"""
+function tog_finished(s::BatchediLQRSolver)
+    slots = Vector{Int32}(undef, s.B)
+    cnt = Ref{Int32}(0)
+    togcheck(ccall((:tog_finished, libtog), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), s.handle, slots, cnt))
+    return slots[1:cnt[]]
+end
+
+function tog_get_slots(s::BatchediLQRSolver, field::Integer, slots::Vector{Int32}, width::Integer)
+    out = Matrix{Float64}(undef, width, length(slots))
+    togcheck(ccall((:tog_get_slots, libtog), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Float64}),
+                   s.handle, Int32(field), Int32(length(slots)), slots, out))
+    return out
+end
+
+function tog_refill!(s::BatchediLQRSolver, slots::Vector{Int32}, x0::Matrix{Float64}, U::Array{Float64,3},
+                     X::Union{Nothing,Array{Float64,3}} = nothing)
+    c = length(slots)
+    size(x0) == (s.n, c) || throw(ArgumentError("x0 must be (n, count)"))
+    size(U) == (s.m, s.N - 1, c) || throw(ArgumentError("U must be (m, N-1, count)"))
+    X === nothing || size(X) == (s.n, s.N, c) || throw(ArgumentError("X must be (n, N, count)"))
+    togcheck(ccall((:tog_refill, libtog), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   s.handle, Int32(c), slots, x0, U, X === nothing ? C_NULL : X))
+    return nothing
+end
+
+function tog_refill_tables!(s::BatchediLQRSolver, slots::Vector{Int32}, lin::Union{Nothing,Array{Float64}},
+                            term::Union{Nothing,Matrix{Float64}}, xf::Union{Nothing,Matrix{Float64}})
+    togcheck(ccall((:tog_refill_tables, libtog), Int32,
+                   (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   s.handle, Int32(length(slots)), slots, lin === nothing ? C_NULL : lin,
+                   term === nothing ? C_NULL : term, xf === nothing ? C_NULL : xf))
+    return nothing
+end
+
+function tog_solve_stream!(s::BatchediLQRSolver, mode::Integer, x0::Matrix{Float64}, U0::Array{Float64,3};
+                           lin::Union{Nothing,Array{Float64}} = nothing, term::Union{Nothing,Matrix{Float64}} = nothing,
+                           xf::Union{Nothing,Matrix{Float64}} = nothing, max_steps::Integer = 0)
+    J = size(x0, 2)
+    size(x0) == (s.n, J) || throw(ArgumentError("x0 must be (n, J)"))
+    size(U0) == (s.m, s.N - 1, J) || throw(ArgumentError("U0 must be (m, N-1, J)"))
+    X = zeros(s.n, s.N, J)
+    U = zeros(s.m, s.N - 1, J)
+    St = zeros(TOG_NSTATS, J)
+    done = Ref{Int64}(0)
+    if lin === nothing && term === nothing && xf === nothing
+        togcheck(ccall((:tog_solve_stream, libtog), Int32,
+                       (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Int32, Ptr{Int64}),
+                       s.handle, Int32(mode), Int64(J), x0, U0, X, U, St, Int32(max_steps), done))
+    else
+        togcheck(ccall((:tog_solve_stream_tables, libtog), Int32,
+                       (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int64}),
+                       s.handle, Int32(mode), Int64(J), x0, U0, lin === nothing ? C_NULL : lin,
+                       term === nothing ? C_NULL : term, xf === nothing ? C_NULL : xf, X, U, St, Int32(max_steps), done))
+    end
+    return X, U, St, Int(done[])
+end
+
 "reset!(solver) (src/solvers.jl:63-67; iLQRSolver's: ρ = dρ = 0, stats cleared, ilqr_solver.jl:146-154)."
 function reset!(s::BatchediLQRSolver)
     empty!(s.stats)

@@ -320,6 +320,18 @@ def load_library(path: os.PathLike | None = None):
     lib.tog_generic_cost_expand.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, C.c_int64] + [_dp] * 6
     lib.tog_generic_cost_expand_device.argtypes = [vp, C.c_int32, vp, vp, C.c_int64] + [vp] * 6 + [vp]
     lib.tog_generic_cost_free.argtypes = [vp]
+    # streamed solves
+    lib.tog_finished.argtypes = [vp, _ip, _ip]
+    lib.tog_get_slots.argtypes = [vp, C.c_int32, C.c_int32, _ip, _dp]
+    lib.tog_refill.argtypes = [vp, C.c_int32, _ip, _dp, _dp, _dp]
+    lib.tog_refill_tables.argtypes = [vp, C.c_int32, _ip, _dp, _dp, _dp]
+    lib.tog_solve_stream.argtypes = [vp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _dp, C.c_int32,
+                                     C.POINTER(C.c_int64)]
+    lib.tog_solve_stream_tables.argtypes = [vp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                            C.c_int32, C.POINTER(C.c_int64)]
+    for name in ("tog_finished", "tog_get_slots", "tog_refill", "tog_refill_tables", "tog_solve_stream",
+                 "tog_solve_stream_tables"):
+        getattr(lib, name).restype = C.c_int32
     for name in ("tog_create", "tog_create_multi", "tog_destroy", "tog_set_stream", "tog_synchronize", "tog_set_state",
                  "tog_set", "tog_get", "tog_get_device_ptr", "tog_dims", "tog_rollout_open_loop",
                  "tog_jacobians", "tog_update_constraints", "tog_cost", "tog_backward_pass",
@@ -351,6 +363,7 @@ EXPORTED_SYMBOLS = (
     "tog_generic_cost_load", "tog_generic_cost_dims", "tog_generic_cost_expand", "tog_generic_cost_expand_device", "tog_generic_cost_free",
     "tog_default_altro_options", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable", "tog_get_pn_history",
     "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs", "tog_set_trajectory_goals",
+    "tog_finished", "tog_get_slots", "tog_refill", "tog_refill_tables", "tog_solve_stream", "tog_solve_stream_tables",
 )
 KERNEL_JACOBIAN, KERNEL_BACKWARD, KERNEL_FORWARD, KERNEL_EXPANSION = 0, 1, 2, 3
 NKERNELS = 4

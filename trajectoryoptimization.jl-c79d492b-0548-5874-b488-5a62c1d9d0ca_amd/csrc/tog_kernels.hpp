@@ -434,6 +434,118 @@ __global__ void __launch_bounds__(64) k_init(const DevProblem* __restrict__ P, D
   Bf.st[b] = s;
 }
 
+// =============================================================================================
+// k_refill: k_init for the listed slots only, from staged inputs (tog_refill, streamed solves)
+// =============================================================================================
+// One wave per listed slot: block i starts job i of the staging buffers (sx0 (n, count), sU (m, N-1, count),
+// sX (n, N, count) or null: X = NaN, the initial rollout) in slot list[i]. The lanes copy the inputs, zero the
+// slot's d (so that the first history record's gradient is a new solver's) and, in an AL solve, set λ = 0 and
+// μ = penalty_initial; lane 0 runs the serial open-loop rollout; then the lanes take the knots (constraint
+// values, stage / terminal cost, AL terms, max_violation partials: k_ls_fallback's and k_al_outer's operations)
+// and lane 0 sums them in traj_cost's order, so every number is k_init's bit for bit. (k_init itself is a lane
+// per trajectory: a serial N-knot chain of scattered loads, 50 µs alone and ~0.5 ms with 9-128 lanes a wave,
+// see k_ls_fallback.) Dynamic LDS: N (2 doubles + 1 int).
+template <class M, int INTEG>
+__global__ void __launch_bounds__(64) k_refill(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
+                                               const int* __restrict__ list, int count,
+                                               const double* __restrict__ sx0, const double* __restrict__ sU,
+                                               const double* __restrict__ sX) {
+  if ((int)blockIdx.x >= count) return;
+  extern __shared__ double rf_lds[];
+  constexpr int n = M::n, m = M::m;
+  const int N = P->N, pmax = P->pmax;
+  const bool al = (mode == TOG_MODE_AL);
+  const long long b = list[blockIdx.x];
+  if (b < 0 || b >= P->B) return;
+  const size_t j = blockIdx.x;
+  const int lane = threadIdx.x;
+  double* sk = rf_lds;      // [N] stage / terminal cost of knot k
+  double* ak = rf_lds + N;  // [N] AL terms of knot k
+  int* hk = reinterpret_cast<int*>(rf_lds + 2 * N);  // [N] knot has rows
+  double* X = Bf.X + (size_t)b * N * n;
+  double* U = Bf.U + (size_t)b * (N - 1) * m;
+  double* d = Bf.d + (size_t)b * (N - 1) * m;
+  double* C = Bf.C + (size_t)b * N * pmax;
+  double* lam = Bf.lam + (size_t)b * N * pmax;
+  double* mu = Bf.mu + (size_t)b * N * pmax;
+  for (int i = lane; i < n; i += WAVE) Bf.x0[(size_t)b * n + i] = sx0[j * n + i];
+  for (int i = lane; i < (N - 1) * m; i += WAVE) {
+    U[i] = sU[j * (size_t)(N - 1) * m + i];
+    d[i] = 0.0;
+  }
+  for (int i = lane; i < N * n; i += WAVE) X[i] = sX ? sX[j * (size_t)N * n + i] : NAN;
+  if (al) {
+    const double mu0 = P->o.penalty_initial;
+    for (int i = lane; i < N * pmax; i += WAVE) {
+      lam[i] = 0.0;
+      mu[i] = mu0;
+    }
+  }
+  __syncthreads();
+  if (lane == 0) traj_rollout_open<M, INTEG>(P, Bf, b);
+  __syncthreads();
+  double cmax = 0.0;
+  for (int k = lane; k < N; k += WAVE) {
+    const double* x = X + (size_t)k * n;
+    const double* u = (k < N - 1) ? U + (size_t)k * m : nullptr;
+    sk[k] = (k < N - 1) ? stage_cost_m<M>(P, b, k, x, u) : terminal_cost_m<M>(P, b, x);
+    const int cnt = al ? knot_count(P, k) : 0;
+    const cptr<ConRow> rows = knot_rows(P, k);
+    double lc = 0.0, cIc = 0.0, e = 0.0, im = -INFINITY;
+    int ni = 0;
+    for (int i = 0; i < cnt; i++) {  // al_knot_terms' operations, then traj_max_violation's
+      const size_t q = (size_t)k * pmax + i;
+      const ConRow r = traj_row(P, b, load_row(rows + i));
+      const double c = row_value_m<M>(r, x, u);
+      const double l = lam[q];
+      const bool a = row_inequality<(ModelTraits<M>::slack > 0)>(r) ? ((c >= 0.0) || (l > 0.0)) : true;
+      const double w = a ? mu[q] : 0.0;
+      lc = fma(l, c, lc);
+      cIc = fma(c * w, c, cIc);
+      C[q] = c;
+      if (row_inequality(r)) {
+        ni++;
+        im = tog_jlmax(im, c);
+      } else {
+        e = tog_jlmax(e, fabs(c));
+      }
+    }
+    if (cnt) {
+      cmax = tog_jlmax(e, cmax);
+      if (ni > 0) cmax = tog_jlmax(tog_jlmax(0.0, im), cmax);
+    }
+    ak[k] = lc + 0.5 * cIc;
+    hk[k] = cnt;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) cmax = tog_jlmax(cmax, __shfl_xor(cmax, off));
+  __syncthreads();
+  if (lane != 0) return;
+  TrajState s = {};
+  s.active = 1;
+  if (al) {
+    s.c_max = cmax;
+    s.mu_max = P->o.penalty_initial;
+    s.al_iter = 1;
+  }
+  set_tolerances(P, s, mode);
+  double J = 0.0, Jc = 0.0;
+  for (int k = 0; k < N - 1; k++) J += sk[k];
+  J += sk[N - 1];
+  for (int k = 0; k < N; k++)
+    if (hk[k]) Jc += ak[k];
+  s.J = al ? J + Jc : J;
+  s.iters = 1;  // record_iteration!(…, J_prev, Inf)
+  s.dJ = INFINITY;
+  s.zero_cnt = 0;
+  s.grad = INFINITY;
+  if (Bf.hist_in) {  // as k_init
+    if (al) hist_outer(Bf, b, s, 0, s.J, s.c_max, s.mu_max);
+    hist_inner(Bf, b, s, s.J, INFINITY, traj_gradient<M>(P, Bf, b, al));
+  }
+  Bf.st[b] = s;
+}
+
 template <class M, int INTEG>
 __global__ void __launch_bounds__(64) k_rollout_open(const DevProblem* __restrict__ P, DevBuffers Bf) {
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -37,6 +37,9 @@ struct ModelOps {
   void (*cost_expansion)(const DevProblem*, const DevBuffers&, long long B, int N, int sqrt, int al, int* fail,
                          hipStream_t);
   void (*init)(const DevProblem*, const DevBuffers&, long long B, int integ, int mode, hipStream_t);
+  // k_refill: init for the `count` slots of a device list, from staged x0, U and X (X null: the initial rollout)
+  void (*refill)(const DevProblem*, const DevBuffers&, int count, int N, int integ, int mode, const int* list,
+                 const double* x0, const double* U, const double* X, hipStream_t);
   void (*rollout_open)(const DevProblem*, const DevBuffers&, long long B, int integ, hipStream_t);
   void (*jacobian)(const DevProblem*, const DevBuffers&, long long B, int N, int integ, hipStream_t);
   void (*backward)(const DevProblem*, const DevBuffers&, long long B, int sqrt, int al, int flags, int team,
@@ -104,6 +107,15 @@ struct ModelLaunch {
     with_integ(integ, [&](auto ic) {
       constexpr int I = decltype(ic)::value;
       hipLaunchKernelGGL((k_init<M, I>), dim3(grid(B, 64)), dim3(64), 0, st, P, Bf, mode);
+    });
+  }
+  static void refill(const DevProblem* P, const DevBuffers& Bf, int count, int N, int integ, int mode, const int* list,
+                     const double* x0, const double* U, const double* X, hipStream_t st) {
+    if (count <= 0) return;
+    const unsigned sm = (unsigned)(N * (2 * sizeof(double) + sizeof(int)));
+    with_integ(integ, [&](auto ic) {
+      constexpr int I = decltype(ic)::value;
+      hipLaunchKernelGGL((k_refill<M, I>), dim3((unsigned)count), dim3(64), sm, st, P, Bf, mode, list, count, x0, U, X);
     });
   }
   static void rollout_open(const DevProblem* P, const DevBuffers& Bf, long long B, int integ, hipStream_t st) {
@@ -438,6 +450,7 @@ struct ModelLaunch {
     o.slack_controls = slack_controls;
     o.cost_expansion = cost_expansion;
     o.init = init;
+    o.refill = refill;
     o.rollout_open = rollout_open;
     o.jacobian = jacobian;
     o.backward = backward;

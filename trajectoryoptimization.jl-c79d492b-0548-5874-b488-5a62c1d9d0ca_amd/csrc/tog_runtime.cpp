@@ -18,6 +18,7 @@
 #include "tog_plugin.hpp"
 #include "tog_host_plan.hpp"
 #include "tog_traj_tables.hpp"
+#include "tog_stream.hpp"
 #include "tog_cost_plugin.hpp"
 
 using namespace tog;
@@ -148,6 +149,22 @@ struct tog_handle {
   std::vector<double> kc_row;
   std::vector<int> goal_idx;  // state index of each terminal goal row, in row order (ng = size)
   std::string goal_err;       // why the problem's goal rows cannot vary per trajectory (empty: they can)
+  // Streamed solves (tog_finished / tog_get_slots / tog_refill / tog_solve_stream), allocated on first use and
+  // freed in tog_destroy; everything is ordered on the handle's stream.
+  // d_slot_job (B): the job a slot holds whose end has not been listed yet (-1: empty, or listed by
+  // k_list_finished); d_fin (1 + B): k_list_finished's count and list; d_gl, d_rl (B each): the slot lists of a
+  // gather and of a refill; h_ints: their pinned host images [fin (1 + B) | gl (B) | rl (B) | jobs (B)].
+  int *d_slot_job = nullptr, *d_fin = nullptr, *d_gl = nullptr, *d_rl = nullptr, *d_rjob = nullptr, *h_ints = nullptr;
+  // staging, a pinned host buffer and its device twin each, grown on demand: refill inputs (x0, U, X, the table
+  // rows) and gathered results
+  struct Stage {
+    double *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+  };
+  Stage sin_x0, sin_U, sin_X, sin_tab, sout;
+  hipEvent_t fin_ev = nullptr, refill_ev = nullptr, gather_ev = nullptr;
+  bool refill_pending = false;
+  long long jobs_started = 0;  // tog_refill's running job index
 };
 
 static hipEvent_t next_event(tog_handle* h) {
@@ -382,6 +399,69 @@ static __global__ void __launch_bounds__(256) k_list_active(const TrajState* __r
   if (lane == leader) base = atomicAdd(count, __popcll(mask));
   base = __shfl(base, leader);
   if (a) list[base + __popcll(mask & ((1ull << lane) - 1))] = (int)b;
+}
+
+// Streamed solves: the slots that hold a job (slot_job >= 0), are inactive and were not listed before, compacted
+// as k_list_active does; a listed slot is marked (slot_job = -1), so every finished job is listed once. out[0] is
+// the count, out + 1 the list.
+static __global__ void __launch_bounds__(256) k_list_finished(const TrajState* __restrict__ st, int* slot_job,
+                                                              long long B, int* out) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool f = b < B && slot_job[b] >= 0 && !st[b].active;
+  const unsigned long long mask = __ballot(f);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll((long long)mask) - 1;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(out, __popcll(mask));
+  base = __shfl(base, leader);
+  if (f) {
+    out[1 + base + __popcll(mask & ((1ull << lane) - 1))] = (int)b;
+    slot_job[b] = -1;
+  }
+}
+
+// slot_job[b] = b: every slot holds the trajectory tog_solve_init started in it
+static __global__ void k_slot_iota(int* slot_job, long long B) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) slot_job[b] = (int)b;
+}
+// every slot empty and inactive (the start of a streamed solve)
+static __global__ void k_slots_clear(TrajState* st, int* slot_job, long long B) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  st[b].active = 0;
+  slot_job[b] = -1;
+}
+// the listed slots hold these jobs from now on (after k_refill)
+static __global__ void k_slots_mark(int* slot_job, const int* __restrict__ list, const int* __restrict__ jobs,
+                                    int count, long long B) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int b = list[i];
+  if (b >= 0 && b < B) slot_job[b] = jobs[i];
+}
+
+// A field's blocks (w doubles per slot) of the listed slots into a contiguous buffer, block i = slot list[i];
+// one workgroup per listed slot, lanes over the block's entries (coalesced both ways). k_scatter_slots is the
+// inverse (the table rows of a refill).
+static __global__ void __launch_bounds__(256) k_gather_slots(const double* __restrict__ src, size_t w,
+                                                             const int* __restrict__ list, long long B,
+                                                             double* __restrict__ dst) {
+  const long long b = list[blockIdx.x];
+  if (b < 0 || b >= B) return;
+  const double* s = src + (size_t)b * w;
+  double* d = dst + (size_t)blockIdx.x * w;
+  for (size_t e = threadIdx.x; e < w; e += blockDim.x) d[e] = s[e];
+}
+static __global__ void __launch_bounds__(256) k_scatter_slots(double* __restrict__ dst, size_t w,
+                                                              const int* __restrict__ list, long long B,
+                                                              const double* __restrict__ src) {
+  const long long b = list[blockIdx.x];
+  if (b < 0 || b >= B) return;
+  const double* s = src + (size_t)blockIdx.x * w;
+  double* d = dst + (size_t)b * w;
+  for (size_t e = threadIdx.x; e < w; e += blockDim.x) d[e] = s[e];
 }
 
 __global__ void k_fill(double* p, size_t count, double v) {
@@ -827,6 +907,12 @@ int32_t tog_destroy(tog_handle* h) {
   if (h->stats_ev) (void)hipEventDestroy(h->stats_ev);
   if (h->sync_ev) (void)hipEventDestroy(h->sync_ev);
   if (h->h_stats) (void)hipHostFree(h->h_stats);
+  // streamed solves: the pinned staging (the device twins are in allocs) and the events
+  if (h->h_ints) (void)hipHostFree(h->h_ints);
+  for (tog_handle::Stage* s : {&h->sin_x0, &h->sin_U, &h->sin_X, &h->sin_tab, &h->sout})
+    if (s->h) (void)hipHostFree(s->h);
+  for (hipEvent_t e : {h->fin_ev, h->refill_ev, h->gather_ev})
+    if (e) (void)hipEventDestroy(e);
   delete h;
   return TOG_OK;
 }
@@ -1324,6 +1410,25 @@ static int put_states(tog_handle* h, const std::vector<TrajState>& st) {
   return TOG_OK;
 }
 
+// a trajectory's TOG_FIELD_STATS row
+static void stats_row(const TrajState& s, double* o) {
+  for (int j = 0; j < TOG_NSTATS; j++) o[j] = 0.0;
+  o[TOG_STAT_J] = s.J;
+  o[TOG_STAT_DJ] = s.dJ;
+  o[TOG_STAT_GRADIENT] = s.grad;
+  o[TOG_STAT_ITERATIONS] = s.iters;
+  o[TOG_STAT_ZERO_COUNT] = s.zero_cnt;
+  o[TOG_STAT_ALPHA] = s.alpha;
+  o[TOG_STAT_Z] = s.z;
+  o[TOG_STAT_C_MAX] = s.c_max;
+  o[TOG_STAT_AL_ITER] = s.al_iter;
+  o[TOG_STAT_TOTAL_STEPS] = s.total_steps;
+  o[TOG_STAT_LS_TRIALS] = s.ls_trials;
+  o[TOG_STAT_BP_RESTARTS] = s.bp_restarts;
+  o[TOG_STAT_FLAGS] = s.flags | (s.active ? TOG_TRAJ_ACTIVE : 0);
+  o[TOG_STAT_PENALTY_MAX] = s.mu_max;
+}
+
 int32_t tog_get(tog_handle* h, int32_t field, double* out) {
   if (!h || !out) return fail(TOG_ERR_ARG, "null argument");
   if (is_multi(h)) {
@@ -1367,22 +1472,7 @@ int32_t tog_get(tog_handle* h, int32_t field, double* out) {
         out[2 * i] = s.rho;
         out[2 * i + 1] = s.drho;
       } else {
-        double* o = out + i * TOG_NSTATS;
-        for (int j = 0; j < TOG_NSTATS; j++) o[j] = 0.0;
-        o[TOG_STAT_J] = s.J;
-        o[TOG_STAT_DJ] = s.dJ;
-        o[TOG_STAT_GRADIENT] = s.grad;
-        o[TOG_STAT_ITERATIONS] = s.iters;
-        o[TOG_STAT_ZERO_COUNT] = s.zero_cnt;
-        o[TOG_STAT_ALPHA] = s.alpha;
-        o[TOG_STAT_Z] = s.z;
-        o[TOG_STAT_C_MAX] = s.c_max;
-        o[TOG_STAT_AL_ITER] = s.al_iter;
-        o[TOG_STAT_TOTAL_STEPS] = s.total_steps;
-        o[TOG_STAT_LS_TRIALS] = s.ls_trials;
-        o[TOG_STAT_BP_RESTARTS] = s.bp_restarts;
-        o[TOG_STAT_FLAGS] = s.flags | (s.active ? TOG_TRAJ_ACTIVE : 0);
-        o[TOG_STAT_PENALTY_MAX] = s.mu_max;
+        stats_row(s, out + i * TOG_NSTATS);
       }
     }
     return TOG_OK;
@@ -1712,6 +1802,9 @@ int32_t tog_solve_init(tog_handle* h, int32_t mode) {
   h->last_active = -1.0;
   h->stats_pending = false;  // a check left open by a failed solve is abandoned (its readback is never read)
   h->ops->init(h->dP, h->buf, h->B, h->integ, mode, h->stream);
+  if (h->d_slot_job)  // every slot holds a trajectory again (tog_finished)
+    hipLaunchKernelGGL(k_slot_iota, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->d_slot_job,
+                       (long long)h->B);
   HIPCHECK(hipGetLastError());
   return TOG_OK;
 }
@@ -1730,9 +1823,12 @@ int32_t tog_solve_step(tog_handle* h, int32_t nsteps) {
   // convergence tail (or a small batch): the latency-sized backward kernels (k_bwd_team WPE = 1)
   h->buf.tail = ((double)h->B <= TAIL_ACTIVE || (h->last_active >= 0.0 && h->last_active <= TAIL_ACTIVE)) ? 1 : 0;
   // In the tail the kernels launch over the active trajectories only: k_list_active lists them once per
-  // call (trajectories only ever finish during a solve, so the list stays a superset of the active set
-  // for the call's steps, and every kernel still checks `active`), and each launch covers
-  // ceil(last n_active readback) slots instead of the whole batch (traj_of_slot, tog_kernels.hpp).
+  // call, and each launch covers ceil(last_active) slots instead of the whole batch (traj_of_slot,
+  // tog_kernels.hpp). Within a call trajectories only ever finish, so the list stays a superset of the active
+  // set for the call's steps, and every kernel still checks `active`. Between calls a slot may start a new
+  // trajectory (tog_refill, the streamed solves): the list is rebuilt by the next call, and the refill keeps
+  // last_active an upper bound of the active count (it adds the slots it refills), so the launch width covers
+  // the new list. Refills therefore happen between tog_solve_step calls only.
   DevBuffers Bt = h->buf;
   long long Bl = h->B;
   if (h->buf.tail && h->last_active >= 0.0 && h->last_active < (double)h->B && !getenv("TOG_NO_COMPACT")) {
@@ -1865,6 +1961,415 @@ int32_t tog_solve(tog_handle* h, int32_t mode, int32_t max_steps) {
     if ((rc = tog_batch_stats_begin(h))) return rc;
   }
   return TOG_OK;
+}
+
+// ------------------------------------------------------------------------------ streamed solves
+// J jobs through the handle's B slots (tog_stream.hpp has the scheduling): k_list_finished lists the slots whose
+// trajectory ended, k_gather_slots packs their results for one device -> host copy, k_refill starts the next
+// jobs in them. The pieces are exported (tog_finished, tog_get_slots, tog_refill, tog_refill_tables);
+// tog_solve_stream is the driver over them.
+extern "C++" {
+static int32_t stream_refuse(const tog_handle* h, const char* who) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (is_multi(h))
+    return fail(TOG_ERR_UNSUPPORTED, std::string(who) + ": not built for tog_create_multi handles (stream one handle per device)");
+  return TOG_OK;
+}
+
+// first use: the slot arrays, their pinned images and the events
+static int32_t stream_alloc(tog_handle* h) {
+  if (h->d_slot_job) return TOG_OK;
+  const size_t B = (size_t)h->B;
+  int rc;
+  int* sj = nullptr;
+  if ((rc = dalloc(h, &sj, B)) || (rc = dalloc(h, &h->d_fin, B + 1)) || (rc = dalloc(h, &h->d_gl, B)) ||
+      (rc = dalloc(h, &h->d_rl, B)) || (rc = dalloc(h, &h->d_rjob, B)))
+    return rc;
+  HIPCHECK(hipHostMalloc((void**)&h->h_ints, sizeof(int) * (4 * B + 1), hipHostMallocDefault));
+  HIPCHECK(hipEventCreateWithFlags(&h->fin_ev, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&h->refill_ev, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&h->gather_ev, hipEventDisableTiming));
+  // (as after tog_solve_init: every slot holds its trajectory)
+  hipLaunchKernelGGL(k_slot_iota, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, sj, (long long)B);
+  HIPCHECK(hipGetLastError());
+  h->d_slot_job = sj;
+  return TOG_OK;
+}
+static int* pin_fin(tog_handle* h) { return h->h_ints; }
+static int* pin_gl(tog_handle* h) { return h->h_ints + (size_t)h->B + 1; }
+static int* pin_rl(tog_handle* h) { return h->h_ints + 2 * (size_t)h->B + 1; }
+static int* pin_rjob(tog_handle* h) { return h->h_ints + 3 * (size_t)h->B + 1; }
+
+// a staging pair of at least `count` doubles (sized for B slots of `per_slot` on first use). Growing waits for
+// the stream, so nothing in flight reads the old buffers.
+static int32_t stage_ensure(tog_handle* h, tog_handle::Stage& s, size_t per_slot, size_t count) {
+  if (count <= s.cap && s.h) return TOG_OK;
+  const size_t want = std::max(count, per_slot * (size_t)h->B);
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  if (s.h) (void)hipHostFree(s.h);
+  dfree(h, s.d);
+  s.h = s.d = nullptr;
+  s.cap = 0;
+  HIPCHECK(hipHostMalloc((void**)&s.h, sizeof(double) * (want ? want : 1), hipHostMallocDefault));
+  const int rc = dalloc(h, &s.d, want);
+  if (rc) return rc;
+  s.cap = want;
+  return TOG_OK;
+}
+
+static int32_t check_slots(const tog_handle* h, int32_t count, const int32_t* slots, bool unique, const char* who) {
+  if (count < 0 || count > h->B) return fail(TOG_ERR_ARG, std::string(who) + ": count must be in [0, B]");
+  if (count > 0 && !slots) return fail(TOG_ERR_ARG, std::string(who) + ": null slot list");
+  std::vector<char> seen(unique ? (size_t)h->B : 0, 0);
+  for (int i = 0; i < count; i++) {
+    if (slots[i] < 0 || slots[i] >= h->B) return fail(TOG_ERR_ARG, std::string(who) + ": slot " + std::to_string(slots[i]) + " out of range");
+    if (unique) {
+      if (seen[(size_t)slots[i]]) return fail(TOG_ERR_ARG, std::string(who) + ": slot " + std::to_string(slots[i]) + " listed twice");
+      seen[(size_t)slots[i]] = 1;
+    }
+  }
+  return TOG_OK;
+}
+
+// enqueue: the blocks of `src` (w doubles a slot) of the device list `dlist` into dst
+static void gather_enqueue(tog_handle* h, const double* src, size_t w, const int* dlist, int count, double* dst) {
+  if (count > 0 && w > 0)
+    hipLaunchKernelGGL(k_gather_slots, dim3((unsigned)count), dim3(256), 0, h->stream, src, w, dlist, (long long)h->B, dst);
+}
+constexpr size_t ST_W = sizeof(TrajState) / sizeof(double);  // a TrajState gathered as doubles
+static_assert(sizeof(TrajState) % sizeof(double) == 0, "TrajState is gathered as whole doubles");
+
+// The refill of `count` slots, enqueued (no wait). Job i's data is row src(i) of the arrays (x0 (n, .),
+// U (m, N-1, .), X (n, N, .) or null, and the table rows lin, term, xf, each null or (width, .)); job_id(i) is
+// what the slot holds from then on. The caller has checked the slots; tables given are tables the handle has.
+template <class Src, class Job>
+static int32_t refill_enqueue(tog_handle* h, int count, const int* slots, Src&& src, Job&& job_id, const double* x0,
+                              const double* U, const double* X, const double* lin, const double* term,
+                              const double* xf) {
+  if (count <= 0) return TOG_OK;
+  int32_t rc;
+  const size_t n = h->n, m = h->m, N = h->N, c = (size_t)count;
+  const size_t wu = (N - 1) * m, wx = N * n;
+  const size_t wl = lin ? tog_traj::lin_width(h->n, h->m, h->N, h->hostP.lin_per_knot) : 0;
+  const size_t wt = term ? tog_traj::term_width(h->n) : 0, wg = xf ? n : 0, ng = h->goal_idx.size();
+  if (!x0) U = X = nullptr;  // (the tables only)
+  if ((x0 && ((rc = stage_ensure(h, h->sin_x0, n, c * n)) || (rc = stage_ensure(h, h->sin_U, wu, c * wu)))) ||
+      (X && (rc = stage_ensure(h, h->sin_X, wx, c * wx))) ||
+      ((wl + wt + wg) && (rc = stage_ensure(h, h->sin_tab, wl + wt + wg, c * (wl + wt + wg)))))
+    return rc;
+  if (h->refill_pending) {  // the previous refill's copies have left the pinned buffers
+    if ((rc = wait_event(h->refill_ev, "tog_refill"))) return rc;
+    h->refill_pending = false;
+  }
+  int *hl = pin_rl(h), *hj = pin_rjob(h);
+  double *tl = h->sin_tab.h, *tt = tl + c * wl, *tg = tt + c * wt;
+  for (size_t i = 0; i < c; i++) {
+    const size_t j = (size_t)src((int)i);
+    hl[i] = slots[i];
+    hj[i] = (int)(job_id((int)i) & 0x7fffffffLL);
+    if (x0) {
+      memcpy(h->sin_x0.h + i * n, x0 + j * n, sizeof(double) * n);
+      memcpy(h->sin_U.h + i * wu, U + j * wu, sizeof(double) * wu);
+    }
+    if (X) memcpy(h->sin_X.h + i * wx, X + j * wx, sizeof(double) * wx);
+    if (lin) memcpy(tl + i * wl, lin + j * wl, sizeof(double) * wl);
+    if (term) memcpy(tt + i * wt, term + j * wt, sizeof(double) * wt);
+    if (xf) {  // the (ng, .) goal values as the device table's (n, .) rows (tog_traj::goal_table)
+      const std::vector<double> g = tog_traj::goal_table(xf + j * ng, h->goal_idx, h->n, 1);
+      memcpy(tg + i * n, g.data(), sizeof(double) * n);
+    }
+  }
+  hipStream_t st = h->stream;
+  HIPCHECK(hipMemcpyAsync(h->d_rl, hl, sizeof(int) * c, hipMemcpyHostToDevice, st));
+  HIPCHECK(hipMemcpyAsync(h->d_rjob, hj, sizeof(int) * c, hipMemcpyHostToDevice, st));
+  if (x0) {
+    HIPCHECK(hipMemcpyAsync(h->sin_x0.d, h->sin_x0.h, sizeof(double) * c * n, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(h->sin_U.d, h->sin_U.h, sizeof(double) * c * wu, hipMemcpyHostToDevice, st));
+  }
+  if (X) HIPCHECK(hipMemcpyAsync(h->sin_X.d, h->sin_X.h, sizeof(double) * c * wx, hipMemcpyHostToDevice, st));
+  if (wl + wt + wg) {
+    HIPCHECK(hipMemcpyAsync(h->sin_tab.d, h->sin_tab.h, sizeof(double) * c * (wl + wt + wg), hipMemcpyHostToDevice, st));
+    const long long B = h->B;
+    double *dl = h->sin_tab.d, *dt = dl + c * wl, *dg = dt + c * wt;
+    if (lin) hipLaunchKernelGGL(k_scatter_slots, dim3((unsigned)c), dim3(256), 0, st, h->d_lin, wl, h->d_rl, B, dl);
+    if (term) hipLaunchKernelGGL(k_scatter_slots, dim3((unsigned)c), dim3(256), 0, st, h->d_term, wt, h->d_rl, B, dt);
+    if (xf) hipLaunchKernelGGL(k_scatter_slots, dim3((unsigned)c), dim3(256), 0, st, h->d_goal, wg, h->d_rl, B, dg);
+  }
+  if (x0) {
+    h->ops->refill(h->dP, h->buf, count, h->N, h->integ, h->mode, h->d_rl, h->sin_x0.d, h->sin_U.d,
+                   X ? h->sin_X.d : nullptr, st);
+    hipLaunchKernelGGL(k_slots_mark, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, st, h->d_slot_job, h->d_rl,
+                       h->d_rjob, count, (long long)h->B);
+    // rule 1 (tog_stream.hpp): last_active stays an upper bound of the active count
+    if (h->last_active >= 0.0) h->last_active = std::min((double)h->B, h->last_active + (double)count);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->refill_ev, st));
+  h->refill_pending = true;
+  return TOG_OK;
+}
+
+// which of the per-trajectory tables a refill may write: only the ones the handle has (its kernel variants
+// were chosen when they were set)
+static int32_t tables_check(const tog_handle* h, const double* lin, const double* term, const double* xf, const char* who) {
+  if ((lin && !h->d_lin) || (term && !h->d_term) || (xf && !h->d_goal))
+    return fail(TOG_ERR_UNSUPPORTED, std::string(who) + ": the handle has no such per-trajectory table (set it with "
+                                                        "tog_set_trajectory_costs / tog_set_trajectory_goals first)");
+  return TOG_OK;
+}
+
+// the device of tog_stream::run over one handle
+struct StreamDev {
+  tog_handle* h;
+  const double *x0, *U0, *lin, *term, *xf;
+  double *X_out, *U_out, *stats_out;
+  std::vector<tog_stream::SlotJob> held;  // the gather in flight
+  std::vector<int> sl;
+  size_t wx() const { return (size_t)h->N * h->n; }
+  size_t wu() const { return (size_t)(h->N - 1) * h->m; }
+
+  int refill(const std::vector<tog_stream::SlotJob>& r) {
+    sl.resize(r.size());
+    for (size_t i = 0; i < r.size(); i++) sl[i] = r[i].slot;
+    return refill_enqueue(
+        h, (int)r.size(), sl.data(), [&](int i) { return r[(size_t)i].job; }, [&](int i) { return r[(size_t)i].job; },
+        x0, U0, nullptr, lin, term, xf);
+  }
+  int step(int nsteps, double hint) {
+    h->last_active = hint;
+    return tog_solve_step(h, nsteps);
+  }
+  int begin_readback() {
+    HIPCHECK(hipMemsetAsync(h->d_fin, 0, sizeof(int), h->stream));
+    hipLaunchKernelGGL(k_list_finished, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->buf.st,
+                       h->d_slot_job, (long long)h->B, h->d_fin);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(pin_fin(h), h->d_fin, sizeof(int) * ((size_t)h->B + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipEventRecord(h->fin_ev, h->stream));
+    return TOG_OK;
+  }
+  int end_readback(std::vector<int>& list) {
+    const int rc = wait_event(h->fin_ev, "tog_solve_stream");
+    if (rc) return rc;
+    const int* p = pin_fin(h);
+    if (p[0] < 0 || p[0] > h->B) return fail(TOG_ERR_DEVICE, "tog_solve_stream: the finished list's count is out of range");
+    list.assign(p + 1, p + 1 + p[0]);
+    std::sort(list.begin(), list.end());  // (the device list's order depends on the blocks' timing)
+    return TOG_OK;
+  }
+  // the results of the gather in flight, out of the pinned buffer, under their jobs
+  int land() {
+    if (held.empty()) return TOG_OK;
+    const int rc = wait_event(h->gather_ev, "tog_solve_stream");
+    if (rc) return rc;
+    const size_t c = held.size();
+    const double *gx = h->sout.h, *gu = gx + c * wx(), *gs = gu + c * wu();
+    for (size_t i = 0; i < c; i++) {
+      const size_t j = (size_t)held[i].job;
+      if (X_out) memcpy(X_out + j * wx(), gx + i * wx(), sizeof(double) * wx());
+      if (U_out) memcpy(U_out + j * wu(), gu + i * wu(), sizeof(double) * wu());
+      if (stats_out) {
+        TrajState s;
+        memcpy(&s, gs + i * ST_W, sizeof(s));
+        stats_row(s, stats_out + j * TOG_NSTATS);
+      }
+    }
+    held.clear();
+    return TOG_OK;
+  }
+  int gather(const std::vector<tog_stream::SlotJob>& g, bool) {
+    int rc = land();  // (one pinned buffer: the previous gather leaves it first; it completed before this readback)
+    if (rc) return rc;
+    const size_t c = g.size(), per = wx() + wu() + ST_W;
+    if ((rc = stage_ensure(h, h->sout, per, c * per))) return rc;
+    int* hl = pin_gl(h);
+    for (size_t i = 0; i < c; i++) hl[i] = g[i].slot;
+    HIPCHECK(hipMemcpyAsync(h->d_gl, hl, sizeof(int) * c, hipMemcpyHostToDevice, h->stream));
+    double *gx = h->sout.d, *gu = gx + c * wx(), *gs = gu + c * wu();
+    gather_enqueue(h, h->buf.X, wx(), h->d_gl, (int)c, gx);
+    gather_enqueue(h, h->buf.U, wu(), h->d_gl, (int)c, gu);
+    gather_enqueue(h, reinterpret_cast<const double*>(h->buf.st), ST_W, h->d_gl, (int)c, gs);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(h->sout.h, h->sout.d, sizeof(double) * c * per, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipEventRecord(h->gather_ev, h->stream));
+    held = g;
+    return TOG_OK;
+  }
+  int flush() { return land(); }
+};
+
+static int32_t solve_stream(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0,
+                            const double* lin, const double* term, const double* xf, double* X_out, double* U_out,
+                            double* stats_out, int32_t max_steps, int64_t* jobs_done, const char* who) {
+  int32_t rc = stream_refuse(h, who);
+  if (rc) return rc;
+  if (jobs_done) *jobs_done = 0;
+  if (mode != TOG_MODE_ILQR && mode != TOG_MODE_AL)
+    return fail(TOG_ERR_UNSUPPORTED, std::string(who) + ": streams run TOG_MODE_ILQR and TOG_MODE_AL solves (projected "
+                                                        "Newton and the ALTRO flows are not streamed)");
+  if (njobs < 0) return fail(TOG_ERR_ARG, std::string(who) + ": njobs < 0");
+  if (njobs > 0 && (!x0 || !U0)) return fail(TOG_ERR_ARG, std::string(who) + ": null x0 or U0");
+  HIPCHECK(hipSetDevice(h->device));
+  if ((rc = stream_alloc(h))) return rc;
+  h->mode = mode;
+  h->stats_pending = false;
+  // every slot empty and inactive; the planner's first refill starts the first min(J, B) jobs
+  hipLaunchKernelGGL(k_slots_clear, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->buf.st,
+                     h->d_slot_job, (long long)h->B);
+  HIPCHECK(hipGetLastError());
+  h->last_active = 0.0;
+  tog_stream::Planner plan((long long)njobs, (int)h->B);
+  StreamDev dev{h, x0, U0, lin, term, xf, X_out, U_out, stats_out, {}, {}};
+  const int r = tog_stream::run(plan, dev, 4, max_steps > 0 ? (long long)max_steps : 0);
+  if (r == -1 && !plan.error().empty()) return fail(TOG_ERR_DEVICE, std::string(who) + ": " + plan.error());
+  if (r) return r;
+  if (stats_out)  // jobs never started: zero rows
+    for (long long j = plan.started(); j < (long long)njobs; j++)
+      memset(stats_out + (size_t)j * TOG_NSTATS, 0, sizeof(double) * TOG_NSTATS);
+  if (jobs_done) *jobs_done = plan.finished();
+  h->last_active = -1.0;  // (no readback of the batch's active count backs a hint after the stream)
+  return TOG_OK;
+}
+}  // extern "C++"
+
+int32_t tog_finished(tog_handle* h, int32_t* slots_out, int32_t* count_out) {
+  int32_t rc = stream_refuse(h, "tog_finished");
+  if (rc) return rc;
+  if (!slots_out || !count_out) return fail(TOG_ERR_ARG, "null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  if ((rc = stream_alloc(h))) return rc;
+  HIPCHECK(hipMemsetAsync(h->d_fin, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_list_finished, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->buf.st,
+                     h->d_slot_job, (long long)h->B, h->d_fin);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(pin_fin(h), h->d_fin, sizeof(int) * ((size_t)h->B + 1), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipEventRecord(h->fin_ev, h->stream));
+  if ((rc = wait_event(h->fin_ev, "tog_finished"))) return rc;
+  const int* p = pin_fin(h);
+  if (p[0] < 0 || p[0] > h->B) return fail(TOG_ERR_DEVICE, "tog_finished: the list's count is out of range");
+  std::vector<int> l(p + 1, p + 1 + p[0]);
+  std::sort(l.begin(), l.end());
+  for (size_t i = 0; i < l.size(); i++) slots_out[i] = l[i];
+  *count_out = (int32_t)l.size();
+  return TOG_OK;
+}
+
+int32_t tog_get_slots(tog_handle* h, int32_t field, int32_t count, const int32_t* slots, double* out) {
+  int32_t rc = stream_refuse(h, "tog_get_slots");
+  if (rc) return rc;
+  if ((rc = check_slots(h, count, slots, false, "tog_get_slots"))) return rc;
+  if (count == 0) return TOG_OK;
+  if (!out) return fail(TOG_ERR_ARG, "null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  if ((rc = stream_alloc(h))) return rc;
+  const bool from_state = field == TOG_FIELD_STATS || field == TOG_FIELD_DV || field == TOG_FIELD_RHO ||
+                          field == TOG_FIELD_HIST_COUNT;
+  if ((field == TOG_FIELD_HIST_INNER || field == TOG_FIELD_HIST_OUTER) && !h->buf.hist_in)
+    return fail(TOG_ERR_ARG, "iteration histories are off (tog_history_enable)");
+  double* p = nullptr;
+  if (!from_state) field_count(h, field, &p);
+  const size_t wo = per_traj(h, field), w = from_state ? ST_W : wo, c = (size_t)count;
+  if (!wo || (!from_state && !p))
+    return fail(TOG_ERR_ARG, "tog_get_slots: field not available per slot (A, B are strided; S, SX need TOG_BP_STORE_S)");
+  if ((rc = stage_ensure(h, h->sout, w, c * w))) return rc;
+  HIPCHECK(hipStreamSynchronize(h->stream));  // (the pinned list and buffer are this call's alone)
+  int* hl = pin_gl(h);
+  for (size_t i = 0; i < c; i++) hl[i] = slots[i];
+  HIPCHECK(hipMemcpyAsync(h->d_gl, hl, sizeof(int) * c, hipMemcpyHostToDevice, h->stream));
+  gather_enqueue(h, from_state ? reinterpret_cast<const double*>(h->buf.st) : p, w, h->d_gl, count, h->sout.d);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(h->sout.h, h->sout.d, sizeof(double) * c * w, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipEventRecord(h->gather_ev, h->stream));
+  if ((rc = wait_event(h->gather_ev, "tog_get_slots"))) return rc;
+  if (!from_state) {
+    memcpy(out, h->sout.h, sizeof(double) * c * w);
+    return TOG_OK;
+  }
+  for (size_t i = 0; i < c; i++) {
+    TrajState s;
+    memcpy(&s, h->sout.h + i * ST_W, sizeof(s));
+    double* o = out + i * wo;
+    if (field == TOG_FIELD_STATS) {
+      stats_row(s, o);
+    } else if (field == TOG_FIELD_DV) {
+      o[0] = s.dV0, o[1] = s.dV1;
+    } else if (field == TOG_FIELD_RHO) {
+      o[0] = s.rho, o[1] = s.drho;
+    } else {
+      o[0] = s.hn_in, o[1] = s.hn_out;
+    }
+  }
+  return TOG_OK;
+}
+
+int32_t tog_refill(tog_handle* h, int32_t count, const int32_t* slots, const double* x0, const double* U, const double* X) {
+  int32_t rc = stream_refuse(h, "tog_refill");
+  if (rc) return rc;
+  if ((rc = check_slots(h, count, slots, true, "tog_refill"))) return rc;
+  if (count == 0) return TOG_OK;
+  if (!x0 || !U) return fail(TOG_ERR_ARG, "null argument");
+  if (h->stats_pending) return fail(TOG_ERR_ARG, "tog_refill: end the pending tog_batch_stats_begin first (its count would miss the refill)");
+  HIPCHECK(hipSetDevice(h->device));
+  if ((rc = stream_alloc(h))) return rc;
+  // no listed slot may still be iterating: their states, gathered
+  std::vector<double> st((size_t)count * TOG_NSTATS);
+  if ((rc = tog_get_slots(h, TOG_FIELD_STATS, count, slots, st.data()))) return rc;
+  for (int i = 0; i < count; i++)
+    if ((int)st[(size_t)i * TOG_NSTATS + TOG_STAT_FLAGS] & TOG_TRAJ_ACTIVE)
+      return fail(TOG_ERR_ARG, "tog_refill: slot " + std::to_string(slots[i]) + " is active");
+  const long long first = h->jobs_started;
+  rc = refill_enqueue(
+      h, count, slots, [](int i) { return (long long)i; }, [&](int i) { return first + i; }, x0, U, X, nullptr,
+      nullptr, nullptr);
+  if (rc) return rc;
+  h->jobs_started += count;
+  HIPCHECK(hipStreamSynchronize(h->stream));  // the caller's arrays and the pinned staging are free again
+  h->refill_pending = false;
+  return TOG_OK;
+}
+
+int32_t tog_refill_tables(tog_handle* h, int32_t count, const int32_t* slots, const double* lin, const double* term,
+                          const double* xf) {
+  int32_t rc = stream_refuse(h, "tog_refill_tables");
+  if (rc) return rc;
+  if ((rc = tables_check(h, lin, term, xf, "tog_refill_tables"))) return rc;
+  if ((rc = check_slots(h, count, slots, true, "tog_refill_tables"))) return rc;
+  if (count == 0 || (!lin && !term && !xf)) return TOG_OK;
+  HIPCHECK(hipSetDevice(h->device));
+  if ((rc = stream_alloc(h))) return rc;
+  // (x0 null: the tables only; k_refill follows with tog_refill)
+  rc = refill_enqueue(
+      h, count, slots, [](int i) { return (long long)i; }, [](int) { return 0LL; }, nullptr, nullptr, nullptr, lin,
+      term, xf);
+  if (rc) return rc;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->refill_pending = false;
+  return TOG_OK;
+}
+
+int32_t tog_solve_stream(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0, double* X_out,
+                         double* U_out, double* stats_out, int32_t max_steps, int64_t* jobs_done) {
+  if (h && !is_multi(h) && (h->d_lin || h->d_term || h->d_goal))
+    return fail(TOG_ERR_ARG, "tog_solve_stream: the handle has per-trajectory cost or goal tables; give every job its "
+                             "rows through tog_solve_stream_tables");
+  return solve_stream(h, mode, njobs, x0, U0, nullptr, nullptr, nullptr, X_out, U_out, stats_out, max_steps, jobs_done,
+                      "tog_solve_stream");
+}
+
+int32_t tog_solve_stream_tables(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0,
+                                const double* lin, const double* term, const double* xf, double* X_out, double* U_out,
+                                double* stats_out, int32_t max_steps, int64_t* jobs_done) {
+  int32_t rc = stream_refuse(h, "tog_solve_stream_tables");
+  if (rc) return rc;
+  if (!h->d_lin && !h->d_term && !h->d_goal)
+    return fail(TOG_ERR_UNSUPPORTED, "tog_solve_stream_tables: the handle has no per-trajectory table (set them with "
+                                     "tog_set_trajectory_costs / tog_set_trajectory_goals first; their kernel "
+                                     "variants are chosen then)");
+  if ((rc = tables_check(h, lin, term, xf, "tog_solve_stream_tables"))) return rc;
+  if (njobs > 0 && ((h->d_lin && !lin) || (h->d_term && !term) || (h->d_goal && !xf)))
+    return fail(TOG_ERR_ARG, "tog_solve_stream_tables: every table the handle has needs the jobs' rows");
+  return solve_stream(h, mode, njobs, x0, U0, lin, term, xf, X_out, U_out, stats_out, max_steps, jobs_done,
+                      "tog_solve_stream_tables");
 }
 
 int32_t tog_profile(tog_handle* h, int32_t enable) {

@@ -214,6 +214,85 @@ class BatchHandle:
         """tog_solve; max_steps None/0: the tog_solve_budget default"""
         abi.check(self.lib, self.lib.tog_solve(self.h, int(mode), int(max_steps or 0)))
 
+    # ------------------------------------------------------------------ streamed solves
+    @staticmethod
+    def _slots(slots):
+        s = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).ravel())
+        return s, s.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def finished(self):
+        """tog_finished: the slots whose trajectory finished and that were not listed before (ascending)."""
+        out = np.empty(self.B, dtype=np.int32)
+        cnt = C.c_int32()
+        abi.check(self.lib, self.lib.tog_finished(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def get_slots(self, field, slots):
+        """tog_get_slots: tog_get's blocks of the listed slots, (count, ...) in list order (raw layout)."""
+        s, sp = self._slots(slots)
+        if field == abi.FIELD_HIST_INNER:
+            shape = (self.hcap, 3)
+        elif field == abi.FIELD_HIST_OUTER:
+            shape = (self.opts.al_iterations + 1, 4)
+        elif field == abi.FIELD_HIST_COUNT:
+            shape = (2,)
+        else:
+            shape = self.shape(field)[1:]
+        out = np.empty((len(s),) + tuple(shape), dtype=np.float64)
+        abi.check(self.lib, self.lib.tog_get_slots(self.h, int(field), len(s), sp, abi.as_dp(out)))
+        return out
+
+    def refill(self, slots, x0, U, X=None):
+        """tog_refill: start new trajectories in the listed (inactive) slots: x0 (count, n), U (count, N-1, m),
+        X (count, N, n) or None (the initial rollout)."""
+        s, sp = self._slots(slots)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(len(s), self.n)
+        U = np.ascontiguousarray(U, dtype=np.float64).reshape(len(s), self.N - 1, self.m)
+        Xp = C.cast(None, C.POINTER(C.c_double))
+        if X is not None:
+            X = np.ascontiguousarray(X, dtype=np.float64).reshape(len(s), self.N, self.n)
+            Xp = abi.as_dp(X)
+        abi.check(self.lib, self.lib.tog_refill(self.h, len(s), sp, abi.as_dp(x0), abi.as_dp(U), Xp))
+
+    def refill_tables(self, slots, lin=None, term=None, xf=None):
+        """tog_refill_tables: the listed slots' rows of the per-trajectory tables the handle has."""
+        s, sp = self._slots(slots)
+        null = C.cast(None, C.POINTER(C.c_double))
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (lin, term, xf)]
+        for a in arrs:
+            if a is not None and a.shape[0] != len(s):
+                raise ValueError("a table needs one row per listed slot")
+        abi.check(self.lib, self.lib.tog_refill_tables(self.h, len(s), sp,
+                                                       *[null if a is None else abi.as_dp(a) for a in arrs]))
+
+    def solve_stream(self, mode, x0, U0, lin=None, term=None, xf=None, max_steps=None):
+        """tog_solve_stream (tog_solve_stream_tables when any of lin, term, xf is given): the J jobs x0 (J, n),
+        U0 (J, N-1, m) through this handle's B slots. Returns (X (J, N, n), U (J, N-1, m), stats (J, NSTATS),
+        jobs_done)."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        U0 = np.ascontiguousarray(U0, dtype=np.float64)
+        J = x0.shape[0]
+        if x0.shape != (J, self.n) or U0.shape != (J, self.N - 1, self.m):
+            raise ValueError(f"x0 must be (J, {self.n}) and U0 (J, {self.N - 1}, {self.m})")
+        X = np.zeros((J, self.N, self.n))
+        U = np.zeros((J, self.N - 1, self.m))
+        S = np.zeros((J, abi.NSTATS))
+        done = C.c_int64()
+        ms = int(max_steps or 0)
+        if lin is None and term is None and xf is None:
+            abi.check(self.lib, self.lib.tog_solve_stream(self.h, int(mode), J, abi.as_dp(x0), abi.as_dp(U0),
+                                                          abi.as_dp(X), abi.as_dp(U), abi.as_dp(S), ms, C.byref(done)))
+        else:
+            null = C.cast(None, C.POINTER(C.c_double))
+            arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (lin, term, xf)]
+            for a in arrs:
+                if a is not None and a.shape[0] != J:
+                    raise ValueError("a table needs one row per job")
+            abi.check(self.lib, self.lib.tog_solve_stream_tables(
+                self.h, int(mode), J, abi.as_dp(x0), abi.as_dp(U0), *[null if a is None else abi.as_dp(a) for a in arrs],
+                abi.as_dp(X), abi.as_dp(U), abi.as_dp(S), ms, C.byref(done)))
+        return X, U, S, int(done.value)
+
     def solve_pn(self, pn_opts: abi.tog_pn_options):
         """tog_solve_pn: returns the (B, PN_NSTATS) statistics rows."""
         out = np.zeros((self.B, abi.PN_NSTATS))

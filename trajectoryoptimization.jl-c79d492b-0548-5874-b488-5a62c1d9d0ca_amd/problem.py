@@ -1000,6 +1000,27 @@ class Problem:
         p._U = self._U[b:b + 1].copy()
         return p
 
+    def batch_slice(self, lo: int, hi: int) -> "Problem":
+        """Trajectories [lo, hi) as a batch of their own: their x0, U, X, and their members of a BatchObjective
+        and of per-trajectory goals (what a streamed solve's handle is created with, solve_stream)."""
+        if not 0 <= lo < hi <= self.B:
+            raise IndexError(f"trajectories [{lo}, {hi}) of {self.B}")
+        p = _copy.copy(self)
+        if isinstance(self.obj, BatchObjective):
+            p.obj = BatchObjective(self.obj.objs[lo:hi])
+        p.constraints = _copy_constraints(self.constraints)
+        memo = {}
+        for k in range(self.N):
+            p.constraints.C[k] = ConstraintSet(
+                memo.setdefault(id(c), GoalConstraint(c.xf[lo:hi])) if isinstance(c, GoalConstraint) and c.batched
+                else c for c in self.constraints[k])
+        p.batched = True
+        p.x0 = self.x0[lo:hi].copy()
+        p.xf = (self.xf[lo:hi] if self.xf.ndim == 2 else self.xf).copy()
+        p._X = self._X[lo:hi].copy()
+        p._U = self._U[lo:hi].copy()
+        return p
+
     # ---- marshalling to the C ABI
     def build_desc(self, tf_min: bool = False) -> abi.DescBuilder:
         """The C ABI's tog_problem_desc. ``tf_min``: mark a tf = 0 problem TOG_PROB_TF_MIN (the original

@@ -608,6 +608,45 @@ def solve_b(prob, solver_or_opts, *, max_steps: int | None = None, device: int =
     return solver
 
 
+def solve_stream(prob, opts, slots: int | None = None, device: int = 0, max_steps: int | None = None):
+    """Continuous batching: ``prob`` holds J jobs (``x0`` (J, n), ``U0`` (J, N-1, m)), solved through a handle of
+    ``min(slots or J, J)`` trajectory slots (tog_solve_stream): a slot whose trajectory finished takes the next
+    job while the others keep iterating, so the convergence tail is paid once, not once per batch. Every job
+    comes out bit for bit as in one ``solve_b`` batch of the J. ``prob.X`` / ``prob.U`` are written in place and
+    the returned solver's ``stats`` are the per-job summary of ``solve_b`` (plus ``jobs_done``); the reference's
+    per-trajectory exceptions are raised after the run. A BatchObjective or per-trajectory goals (J of them) go
+    through tog_solve_stream_tables. ``max_steps``: batch-step bound (None: each job's own iteration limits);
+    jobs unfinished then keep TRAJ_ACTIVE in their flags, jobs never started have zero statistics."""
+    from .problem import BatchObjective
+
+    if isinstance(opts, (ALTROSolverOptions, ProjectedNewtonSolverOptions)) or isinstance(opts, AbstractSolver):
+        raise ValueError("solve_stream takes iLQRSolverOptions or AugmentedLagrangianSolverOptions (ALTRO's composite "
+                         "flows and projected Newton are not streamed)")
+    if isinstance(opts, AugmentedLagrangianSolverOptions) and not prob.is_constrained():
+        opts = opts.opts_uncon  # as solve_b (augmented_lagrangian_methods.jl:33-36)
+    J = prob.B
+    B = min(int(slots) if slots else J, J)
+    if B < 1:
+        raise ValueError("solve_stream needs at least one slot")
+    if not np.isnan(prob._X).all():
+        raise ValueError("solve_stream starts every job from its controls (prob.X must be NaN: the initial rollout)")
+    solver = AbstractSolverFor(prob.batch_slice(0, B), opts, device=device)
+    h = solver.handle
+    lin = term = xf = None
+    if isinstance(prob.obj, BatchObjective):
+        lin, term = prob.obj.lin, prob.obj.term
+        h.set_trajectory_costs(lin[:B], term[:B])  # (the J jobs' table layout, whatever the first B members' own)
+    xf = prob.trajectory_goals()
+    X, U, S, done = h.solve_stream(solver.mode, prob.x0, prob._U, lin=lin, term=term, xf=xf, max_steps=max_steps)
+    prob._X[...] = X
+    prob._U[...] = U
+    solver.stats = stats_dict(S)
+    solver.stats["jobs_done"] = done
+    solver.history = None
+    _raise_trajectory_errors(solver.stats["flags"])
+    return solver
+
+
 def _default_max_steps(solver):
     """tog_solve_budget: the iteration budget times the line-search rounds an iteration may spread
     over in pending mode, so every trajectory reaches its own iteration limit (MAX_ITERS)."""
