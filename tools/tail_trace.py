@@ -1,6 +1,7 @@
 """Attribute a kernel trace of tools/tail_solve.py (rocprofv3 --kernel-trace database).
 
-    python tools/tail_trace.py gpurun_out/<dir>/run_results.db [--last 4000] > profiles/r5_tail_trace.txt
+    python tools/tail_trace.py <trace dir>/run_results.db [--last 4000] [--width-kernel k_ls_spec_tail2]
+        [--top 12] > profiles/r5_tail_trace.txt
 
 Over the last `--last` dispatches (the steady tail): busy time per kernel (calls, total, average),
 and the idle time between consecutive dispatches split by the kernel that follows the gap, so that a
@@ -49,10 +50,12 @@ def main(path, last=4000):
               f"{1e3 * g[2]:10.2f}")
 
 
-def by_width(path, kernel="k_bwd", marker="k_jacobian"):
+def by_width(path, kernel="k_bwd", marker="k_jacobian", top_n=7):
     """Batch steps (delimited by `marker` dispatches) binned by the launch width of the backward kernel
     (its workgroup count = ceil(n_active) of the last readback in a compacted tail launch): steps, mean
-    step time and the mean time of each kernel per step in that bin."""
+    step time and the mean time of each kernel per step in that bin. The team backward packs four
+    trajectories into a workgroup, so where the tail may take it (--width-kernel) bin by a kernel that
+    always launches one workgroup per slot, such as k_ls_spec_tail2."""
     c = sqlite3.connect(path)
     rows = list(c.execute("select name, start, end, grid_x, workgroup_x from kernels order by start"))
     steps, cur = [], None
@@ -91,7 +94,7 @@ def by_width(path, kernel="k_bwd", marker="k_jacobian"):
         for st in sel:
             for k, v in st["k"].items():
                 ks[k] += v / len(sel)
-        top = ", ".join(f"{k} {v:.0f}" for k, v in sorted(ks.items(), key=lambda kv: -kv[1])[:7])
+        top = ", ".join(f"{k} {v:.0f}" for k, v in sorted(ks.items(), key=lambda kv: -kv[1])[:top_n])
         print(f"{lo:5d}-{hi:<6d} {len(sel):6d} {sum(dur) / len(dur):9.4f} {sum(dur) / len(dur) * len(sel) / 1e3:8.3f}  {top}")
 
 
@@ -105,5 +108,14 @@ if __name__ == "__main__":
         i = args.index("--last")
         last = int(args[i + 1])
         del args[i:i + 2]
+    wk, top_n = "k_bwd", 7
+    if "--width-kernel" in args:
+        i = args.index("--width-kernel")
+        wk = args[i + 1]
+        del args[i:i + 2]
+    if "--top" in args:
+        i = args.index("--top")
+        top_n = int(args[i + 1])
+        del args[i:i + 2]
     main(args[0], last)
-    by_width(args[0])
+    by_width(args[0], kernel=wk, top_n=top_n)

@@ -19,6 +19,18 @@ inline void pick(int v, F&& f) {
   (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
+// The square-root backward kernel of a convergence-tail launch over `width` trajectories on a device of `cus`
+// compute units. The quad kernel (k_bwd_quad: a 256-thread workgroup per trajectory under a one-wave-per-SIMD
+// register budget, so one workgroup is resident per CU) takes ceil(width / cus) rounds of its single-trajectory
+// latency. The one-wave team kernel (k_bwd_team at one wave per SIMD, four trajectories per wave) takes one
+// round of about twice that latency for any tail width. Quad while the launch fits TAIL_QUAD_ROUNDS resident
+// rounds, team above (DESIGN.md §5 has the measured times on either side of the boundary).
+enum TailBackward { TAIL_BWD_TEAM = 0, TAIL_BWD_QUAD = 1 };
+constexpr long long TAIL_QUAD_ROUNDS = 1;
+inline TailBackward tail_backward(long long width, int cus) {
+  return (cus > 0 && width <= TAIL_QUAD_ROUNDS * (long long)cus) ? TAIL_BWD_QUAD : TAIL_BWD_TEAM;
+}
+
 // upper Cholesky (dpotrf 'U') of a symmetric matrix; returns false if not PD
 inline bool chol_upper(const double* A, int n, double* U) {
   for (int i = 0; i < n * n; i++) U[i] = 0.0;

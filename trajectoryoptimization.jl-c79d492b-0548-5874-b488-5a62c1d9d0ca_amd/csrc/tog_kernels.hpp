@@ -2877,6 +2877,66 @@ __global__ void __launch_bounds__(64) k_ls_commit(const DevProblem* __restrict__
 // values its replay recomputes, and the gradient terms are summed in the replay's knot order.
 // ls_win: accepted trial j >= 0; -2: max line-search iterations (X̄ = X fallback); -3: accepted with
 // no evaluated trial (J_prev NaN), replayed at α = 0 by k_ls_book.
+// The bodies of the five kernels are per-trajectory __device__ functions, shared with k_ls_finish (below), which
+// runs them in order in one workgroup per trajectory.
+//
+// ls_decide_traj: the acceptance loop of an active trajectory b over its stored trials [0, hi), on one lane.
+// Returns 0: not settled by those trials; 1: settled; 2: the line search ran out of trials (settled, win = -2;
+// the caller lists b for k_ls_fallback, or runs the fallback itself).
+__device__ inline int ls_decide_traj(const DevProblem* __restrict__ P, const DevBuffers& Bf, long long b, int hi,
+                                     int bookkeeping, const double* __restrict__ Jprev_in, int pend) {
+  TrajState* st = Bf.st + b;
+  const tog_options& o = P->o;
+  const int NC = Bf.nc;
+  const double J_prev = bookkeeping ? st->J : Jprev_in[b];
+  const double dV0 = st->dV0, dV1 = st->dV1;
+  if (pend) hi = (st->ls_pend + hi < NC) ? st->ls_pend + hi : NC;  // trials stored so far
+  double J = INFINITY, z = -1.0, expected = 0.0, alpha_last = 0.0;
+  int trials = 0, state = 0, win = -1;
+  for (int jj = 0;; jj++) {
+    if (!((z <= o.line_search_lower_bound || z > o.line_search_upper_bound) && J >= J_prev)) {
+      state = 1;
+      break;
+    }
+    if (jj > o.iterations_linesearch) {
+      state = 2;
+      break;
+    }
+    if (jj >= hi) break;  // not settled by the trials evaluated so far
+    trials++;
+    if (!Bf.lsok[b * NC + jj]) continue;
+    const double aj = ldexp(1.0, -jj);
+    J = Bf.lsJ[b * NC + jj];
+    expected = -aj * (dV0 + aj * dV1);
+    z = (expected > 0.0) ? (J_prev - J) / expected : -1.0;
+    alpha_last = aj;
+    win = jj;
+  }
+  if (state == 0) {
+    if (pend) {  // continue in the next batch step (no Jacobians / backward pass for it meanwhile)
+      st->ls_pend = hi;
+      Bf.ls_win[b] = -9;
+    }
+    return 0;
+  }
+  st->ls_pend = 0;
+  if (state == 2) {  // forward_pass.jl:22-37: z = expected = α = 0, J from cost(X) (the fallback)
+    win = -2;
+    z = 0.0;
+    expected = 0.0;
+    alpha_last = 0.0;
+  } else if (win < 0) {
+    win = -3;
+  }
+  st->alpha = alpha_last;
+  st->z = z;
+  st->expected = expected;
+  st->ls_trials = trials;
+  Bf.ls_win[b] = win;
+  Bf.ls_Jw[b] = J;
+  return state;
+}
+
 template <class M>
 __global__ void __launch_bounds__(256) k_ls_decide(const DevProblem* __restrict__ P, DevBuffers Bf, int hi,
                                                    int bookkeeping, const double* __restrict__ Jprev_in,
@@ -2888,58 +2948,10 @@ __global__ void __launch_bounds__(256) k_ls_decide(const DevProblem* __restrict_
   long long b = 0;
   if (t < nb) {
     b = in_list ? (long long)in_list[t] : traj_of_slot(Bf, t, P->B);
-    TrajState* st = Bf.st + b;
-    if (st->active) {
-      const tog_options& o = P->o;
-      const int NC = Bf.nc;
-      const double J_prev = bookkeeping ? st->J : Jprev_in[b];
-      const double dV0 = st->dV0, dV1 = st->dV1;
-      if (pend) hi = (st->ls_pend + hi < NC) ? st->ls_pend + hi : NC;  // trials stored so far
-      double J = INFINITY, z = -1.0, expected = 0.0, alpha_last = 0.0;
-      int trials = 0, state = 0, win = -1;
-      for (int jj = 0;; jj++) {
-        if (!((z <= o.line_search_lower_bound || z > o.line_search_upper_bound) && J >= J_prev)) {
-          state = 1;
-          break;
-        }
-        if (jj > o.iterations_linesearch) {
-          state = 2;
-          break;
-        }
-        if (jj >= hi) break;  // not settled by the trials evaluated so far
-        trials++;
-        if (!Bf.lsok[b * NC + jj]) continue;
-        const double aj = ldexp(1.0, -jj);
-        J = Bf.lsJ[b * NC + jj];
-        expected = -aj * (dV0 + aj * dV1);
-        z = (expected > 0.0) ? (J_prev - J) / expected : -1.0;
-        alpha_last = aj;
-        win = jj;
-      }
-      if (state == 0) {
-        und = true;
-        if (pend) {  // continue in the next batch step (no Jacobians / backward pass for it meanwhile)
-          st->ls_pend = hi;
-          Bf.ls_win[b] = -9;
-        }
-      } else {
-        st->ls_pend = 0;
-        if (state == 2) {  // forward_pass.jl:22-37: z = expected = α = 0, J from cost(X) (k_ls_fallback)
-          win = -2;
-          z = 0.0;
-          expected = 0.0;
-          alpha_last = 0.0;
-          if (Bf.ls_fb) Bf.ls_fb[atomicAdd(Bf.ls_count + 2, 1)] = (int)b;
-        } else if (win < 0) {
-          win = -3;
-        }
-        st->alpha = alpha_last;
-        st->z = z;
-        st->expected = expected;
-        st->ls_trials = trials;
-        Bf.ls_win[b] = win;
-        Bf.ls_Jw[b] = J;
-      }
+    if (Bf.st[b].active) {
+      const int state = ls_decide_traj(P, Bf, b, hi, bookkeeping, Jprev_in, pend);
+      und = (state == 0);
+      if (state == 2 && Bf.ls_fb) Bf.ls_fb[atomicAdd(Bf.ls_count + 2, 1)] = (int)b;
     }
   }
   if (!out_list || pend) return;
@@ -2953,22 +2965,15 @@ __global__ void __launch_bounds__(256) k_ls_decide(const DevProblem* __restrict_
   if (und) out_list[base + __popcll(mask & ((1ull << lane) - 1))] = (int)b;
 }
 
+// ls_apply_quad: quad r = k Q + q of the accepted trial w >= 0 of trajectory b, on one lane: reads the winner's
+// 32-byte quad, writes its X / U elements (X̄ / Ū at step level) and, on the knot's first quad, its todorov term
 template <class M>
-__global__ void __launch_bounds__(256) k_ls_apply(const DevProblem* __restrict__ P, DevBuffers Bf, int bookkeeping) {
-  // one lane per (trajectory, knot, quad): reads the winner's 32-byte quad, writes its X / U elements
+__device__ __forceinline__ void ls_apply_quad(const DevProblem* __restrict__ P, const DevBuffers& Bf, long long b,
+                                              unsigned r, int w, int bookkeeping) {
   constexpr int n = M::n, m = M::m, Q = cand_q<M>();
   const int N = P->N;
   const unsigned per = (unsigned)N * Q;
-  const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long slot = (long long)(t / per);
-  if (slot >= slot_count(Bf, P->B)) return;
-  const long long b = traj_of_slot(Bf, slot, P->B);
-  const unsigned r = (unsigned)(t - (unsigned long long)slot * per);
   const int k = (int)(r / Q), q = (int)(r - (unsigned)k * Q);
-  if (!Bf.st[b].active) return;
-  const int w = Bf.ls_win[b];
-  if (w < 0) return;
-  if (bookkeeping && Bf.ls_Jw[b] > P->o.max_cost_value) return;  // ilqr_methods.jl:25-28: X̄ not copied
   const int ncp = Bf.ncp;
   const double* tb = Bf.cand + (size_t)b * per * ncp * 4;  // trajectory b's candidates
   const double* src = tb + ((size_t)r * ncp + w) * 4;      // quad q of knot k of trial w
@@ -2999,6 +3004,22 @@ __global__ void __launch_bounds__(256) k_ls_apply(const DevProblem* __restrict__
   }
 }
 
+template <class M>
+__global__ void __launch_bounds__(256) k_ls_apply(const DevProblem* __restrict__ P, DevBuffers Bf, int bookkeeping) {
+  // one lane per (trajectory, knot, quad)
+  const unsigned per = (unsigned)P->N * cand_q<M>();
+  const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long slot = (long long)(t / per);
+  if (slot >= slot_count(Bf, P->B)) return;
+  const long long b = traj_of_slot(Bf, slot, P->B);
+  const unsigned r = (unsigned)(t - (unsigned long long)slot * per);
+  if (!Bf.st[b].active) return;
+  const int w = Bf.ls_win[b];
+  if (w < 0) return;
+  if (bookkeeping && Bf.ls_Jw[b] > P->o.max_cost_value) return;  // ilqr_methods.jl:25-28: X̄ not copied
+  ls_apply_quad<M>(P, Bf, b, r, w, bookkeeping);
+}
+
 // k_ls_book's replay of an accepted trajectory without an evaluated trial (win -3, J_prev NaN): a serial
 // rollout, kept out of line so that the bookkeeping kernel's common path does not carry its registers
 template <class M, int INTEG>
@@ -3020,15 +3041,13 @@ __device__ __noinline__ void replay_cost(const DevProblem* __restrict__ P, const
 // the todorov term max_i |d_i| / (|u_i| + 1) into gk; lane 0 sums the knots in traj_cost's order (stage
 // costs, terminal cost, then the AL terms), so J is traj_cost's bit for bit. (On one lane per trajectory
 // this was a serial 101-knot chain of scattered loads: 50 µs at one trajectory, 0.5 ms at 16-128.)
+// ls_fallback_knots: the per-knot part for trajectory b, lane `lane` of one wave over the knots, into fb_lds
+// (N (2 doubles + 1 int)); ls_fallback_sum: lane 0's sum, after a barrier.
 template <class M>
-__global__ void __launch_bounds__(64) k_ls_fallback(const DevProblem* __restrict__ P, DevBuffers Bf, int al,
-                                                    const int* __restrict__ list, const int* __restrict__ count) {
-  if ((int)blockIdx.x >= *count) return;
-  extern __shared__ double fb_lds[];
+__device__ __forceinline__ void ls_fallback_knots(const DevProblem* __restrict__ P, const DevBuffers& Bf, int al,
+                                                  long long b, int lane, double* fb_lds) {
   constexpr int n = M::n, m = M::m;
   const int N = P->N, pmax = P->pmax;
-  const long long b = list[blockIdx.x];
-  const int lane = threadIdx.x;
   double* sk = fb_lds;       // [N] stage / terminal cost of knot k
   double* ak = fb_lds + N;   // [N] AL terms of knot k
   int* hk = reinterpret_cast<int*>(fb_lds + 2 * N);  // [N] knot has rows
@@ -3068,8 +3087,13 @@ __global__ void __launch_bounds__(64) k_ls_fallback(const DevProblem* __restrict
       Bf.gk[(size_t)b * N + k] = mx;
     }
   }
-  __syncthreads();
-  if (lane != 0) return;
+}
+__device__ inline void ls_fallback_sum(const DevProblem* __restrict__ P, const DevBuffers& Bf, int al, long long b,
+                                       const double* fb_lds) {
+  const int N = P->N;
+  const double* sk = fb_lds;
+  const double* ak = fb_lds + N;
+  const int* hk = reinterpret_cast<const int*>(fb_lds + 2 * N);
   double J = 0.0, Jc = 0.0;
   for (int k = 0; k < N - 1; k++) J += sk[k];
   J += sk[N - 1];
@@ -3078,22 +3102,28 @@ __global__ void __launch_bounds__(64) k_ls_fallback(const DevProblem* __restrict
   Bf.ls_Jw[b] = al ? J + Jc : J;
 }
 
+template <class M>
+__global__ void __launch_bounds__(64) k_ls_fallback(const DevProblem* __restrict__ P, DevBuffers Bf, int al,
+                                                    const int* __restrict__ list, const int* __restrict__ count) {
+  if ((int)blockIdx.x >= *count) return;
+  extern __shared__ double fb_lds[];
+  const long long b = list[blockIdx.x];
+  ls_fallback_knots<M>(P, Bf, al, b, (int)threadIdx.x, fb_lds);
+  __syncthreads();
+  if (threadIdx.x == 0) ls_fallback_sum(P, Bf, al, b, fb_lds);
+}
+
+// ls_book_traj: the bookkeeping of trajectory b (active, line search not pending), on one lane. Returns true
+// when the AL outer update is due: the caller lists b for k_al_outer, or runs the update itself.
 template <class M, int INTEG>
-__global__ void __launch_bounds__(64) k_ls_book(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
-                                                int bookkeeping, const double* Jprev_in, double* Jout) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  extern __shared__ double rt_lds[];
-  const RowTables RT =
-      (mode == TOG_MODE_AL && Bf.rows_lds > 0) ? block_row_tables(P, rt_lds) : global_row_tables(P);
-  if (t >= slot_count(Bf, P->B)) return;
-  const long long b = traj_of_slot(Bf, t, P->B);
-  if (!Bf.st[b].active) return;
+__device__ __forceinline__ bool ls_book_traj(const DevProblem* __restrict__ P, const DevBuffers& Bf, long long b,
+                                             int win, int mode, int bookkeeping, const double* Jprev_in,
+                                             double* Jout, const RowTables& RT) {
   constexpr int n = M::n, m = M::m;
   const tog_options& o = P->o;
   const bool al = (mode == TOG_MODE_AL);
   const int N = P->N;
-  const int win = Bf.ls_win[b];
-  if (win == -9) return;  // line search still pending
+  bool outer = false;
   TrajState s = Bf.st[b];
   double J = Bf.ls_Jw[b];
   const double J_prev = bookkeeping ? s.J : Jprev_in[b];
@@ -3137,12 +3167,29 @@ __global__ void __launch_bounds__(64) k_ls_book(const DevProblem* __restrict__ P
   if (bookkeeping) {
     if (s.flags & TOG_TRAJ_COST_INCREASED) {
       s.active = 0;  // reference: error("Cost increased during Forward Pass")
-    } else if (inner_bookkeeping(P, Bf, b, s, J, grad, mode)) {
-      // the AL outer update runs wave-parallel over the knots in k_al_outer
-      Bf.ls_done[atomicAdd(Bf.ls_count + 1, 1)] = (int)b;
+    } else {
+      outer = inner_bookkeeping(P, Bf, b, s, J, grad, mode);
     }
   }
   Bf.st[b] = s;
+  return outer;
+}
+
+template <class M, int INTEG>
+__global__ void __launch_bounds__(64) k_ls_book(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
+                                                int bookkeeping, const double* Jprev_in, double* Jout) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  extern __shared__ double rt_lds[];
+  const RowTables RT =
+      (mode == TOG_MODE_AL && Bf.rows_lds > 0) ? block_row_tables(P, rt_lds) : global_row_tables(P);
+  if (t >= slot_count(Bf, P->B)) return;
+  const long long b = traj_of_slot(Bf, t, P->B);
+  if (!Bf.st[b].active) return;
+  const int win = Bf.ls_win[b];
+  if (win == -9) return;  // line search still pending
+  // the AL outer update runs wave-parallel over the knots in k_al_outer
+  if (ls_book_traj<M, INTEG>(P, Bf, b, win, mode, bookkeeping, Jprev_in, Jout, RT))
+    Bf.ls_done[atomicAdd(Bf.ls_count + 1, 1)] = (int)b;
 }
 
 // AL outer update (augmented_lagrangian_methods.jl:53-126) of the trajectories k_ls_book listed, one
@@ -3151,17 +3198,16 @@ __global__ void __launch_bounds__(64) k_ls_book(const DevProblem* __restrict__ P
 // and the knot's stage cost and AL terms at the updated multipliers (the next outer iteration's J).
 // The knot terms are summed by lane 0 in traj_cost's order, so J is bit-identical to the serial
 // update's; the maxima are order-independent (NaN-propagating max).
+// al_outer_knots: the per-knot part for trajectory b on one whole wave (lane `lane` over the knots, then the
+// wave's reduction of the maxima), into alo_lds (N (2 doubles + 1 int)); al_outer_sum: lane 0's part, after a
+// barrier.
 template <class M>
-__global__ void __launch_bounds__(64) k_al_outer(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
-                                                 const int* __restrict__ list, const int* __restrict__ count) {
-  if ((int)blockIdx.x >= *count) return;
-  extern __shared__ double alo_lds[];
+__device__ __forceinline__ void al_outer_knots(const DevProblem* __restrict__ P, const DevBuffers& Bf, long long b,
+                                               int lane, double* alo_lds, double& mumax_out, double& cmax_out) {
   constexpr int n = M::n, m = M::m;
   constexpr bool SL = ModelTraits<M>::slack > 0;
   const int N = P->N, pmax = P->pmax;
   const tog_options& o = P->o;
-  const long long b = list[blockIdx.x];
-  const int lane = threadIdx.x;
   double* sk = alo_lds;       // [N] stage / terminal cost of knot k
   double* ak = alo_lds + N;   // [N] λ'c + ½c'Iμc of knot k (NaN-free flag in hk)
   int* hk = reinterpret_cast<int*>(alo_lds + 2 * N);  // [N] knot has rows
@@ -3215,8 +3261,17 @@ __global__ void __launch_bounds__(64) k_al_outer(const DevProblem* __restrict__ 
     mumax = fmax(mumax, __shfl_xor(mumax, off));
     cmax = tog_jlmax(cmax, __shfl_xor(cmax, off));
   }
-  __syncthreads();
-  if (lane != 0) return;
+  mumax_out = mumax;
+  cmax_out = cmax;
+}
+template <class M>
+__device__ __forceinline__ void al_outer_sum(const DevProblem* __restrict__ P, const DevBuffers& Bf, int mode,
+                                             long long b, const double* alo_lds, double mumax, double cmax) {
+  const int N = P->N;
+  const tog_options& o = P->o;
+  const double* sk = alo_lds;
+  const double* ak = alo_lds + N;
+  const int* hk = reinterpret_cast<const int*>(alo_lds + 2 * N);
   TrajState s = Bf.st[b];
   const bool conv = (o.kickout_max_penalty && mumax == o.penalty_max) || (cmax < o.constraint_tolerance);
   double Jnext = 0.0;
@@ -3233,6 +3288,68 @@ __global__ void __launch_bounds__(64) k_al_outer(const DevProblem* __restrict__ 
   const double gnext = (Bf.hist_in && !conv && s.al_iter < o.al_iterations) ? traj_gradient<M>(P, Bf, b, true) : 0.0;
   al_outer_finish(P, Bf, b, s, mumax, cmax, s.J, Jnext, gnext, mode);
   Bf.st[b] = s;
+}
+
+template <class M>
+__global__ void __launch_bounds__(64) k_al_outer(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
+                                                 const int* __restrict__ list, const int* __restrict__ count) {
+  if ((int)blockIdx.x >= *count) return;
+  extern __shared__ double alo_lds[];
+  const long long b = list[blockIdx.x];
+  double mumax, cmax;
+  al_outer_knots<M>(P, Bf, b, (int)threadIdx.x, alo_lds, mumax, cmax);
+  __syncthreads();
+  if (threadIdx.x == 0) al_outer_sum<M>(P, Bf, mode, b, alo_lds, mumax, cmax);
+}
+
+// The finish of the single-round candidate-copy line search at solve level (bookkeeping, convergence tail) in
+// one launch: one workgroup per slot runs k_ls_decide's, k_ls_apply's, k_ls_fallback's, k_ls_book's and
+// k_al_outer's per-trajectory functions in that order, with barriers in between. Everything they hand on is
+// per trajectory, so the verdicts travel through LDS and the rest through global memory the workgroup itself
+// wrote before a barrier: no lists, no counters. Each operation runs on the lanes' data it ran on before (one
+// lane decides and books, lanes over the winner's quads, one wave over the knots), so every result is the
+// split kernels' bit for bit. Dynamic LDS: the larger of N (2 doubles + 1 int) and DevBuffers::rows_lds.
+constexpr int LS_FINISH_THREADS = 256;
+template <class M, int INTEG>
+__global__ void __launch_bounds__(LS_FINISH_THREADS) k_ls_finish(const DevProblem* __restrict__ P, DevBuffers Bf,
+                                                                 int mode, const double* Jprev_in, double* Jout) {
+  extern __shared__ double fin_lds[];
+  __shared__ int v_win, v_fb, v_outer;
+  __shared__ double v_J;
+  const long long b = traj_of_slot(Bf, blockIdx.x, P->B);
+  if (b < 0) return;
+  if (!Bf.st[b].active) return;  // (`active` changes only after the last read of it below)
+  const int tid = threadIdx.x;
+  const bool al = (mode == TOG_MODE_AL);
+  if (tid == 0) {
+    v_fb = (ls_decide_traj(P, Bf, b, Bf.nc, 1, Jprev_in, 0) == 2);
+    v_win = Bf.ls_win[b];
+    v_J = Bf.ls_Jw[b];
+    v_outer = 0;
+  }
+  __syncthreads();
+  const int win = v_win;
+  if (win == -9) return;  // line search still pending
+  if (win >= 0 && !(v_J > P->o.max_cost_value)) {  // ilqr_methods.jl:25-28: X̄ not copied above max_cost_value
+    const unsigned per = (unsigned)P->N * cand_q<M>();
+    for (unsigned r = tid; r < per; r += LS_FINISH_THREADS) ls_apply_quad<M>(P, Bf, b, r, win, 1);
+  }
+  if (v_fb) {
+    if (tid < WAVE) ls_fallback_knots<M>(P, Bf, al ? 1 : 0, b, tid, fin_lds);
+    __syncthreads();
+    if (tid == 0) ls_fallback_sum(P, Bf, al ? 1 : 0, b, fin_lds);
+  }
+  // (the row tables serve the replay of win -3 only, which excludes the fallback's use of the same LDS)
+  const RowTables RT =
+      (win == -3 && al && Bf.rows_lds > 0) ? block_row_tables(P, fin_lds) : global_row_tables(P);
+  __syncthreads();
+  if (tid == 0) v_outer = ls_book_traj<M, INTEG>(P, Bf, b, win, mode, 1, Jprev_in, Jout, RT) ? 1 : 0;
+  __syncthreads();
+  if (!v_outer) return;
+  double mumax = 0.0, cmax = 0.0;
+  if (tid < WAVE) al_outer_knots<M>(P, Bf, b, tid, fin_lds, mumax, cmax);
+  __syncthreads();
+  if (tid == 0) al_outer_sum<M>(P, Bf, mode, b, fin_lds, mumax, cmax);
 }
 
 // =============================================================================================

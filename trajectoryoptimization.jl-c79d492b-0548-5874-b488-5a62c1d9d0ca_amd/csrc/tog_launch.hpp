@@ -169,10 +169,12 @@ struct ModelLaunch {
           });
         });
       };
-      // TOG_BWD_TAIL: "quad" (default) or "team" (the one-wave team kernel), for A/B checks (read per
-      // launch: tests switch it within one process)
+      // quad or the one-wave team kernel by the launch width (tog_plan::tail_backward); TOG_BWD_TAIL = "quad" or
+      // "team" forces either, for A/B checks (read per launch: tests switch it within one process)
       const char* tk = getenv("TOG_BWD_TAIL");
-      const bool quad = !(tk && !strcmp(tk, "team"));
+      const bool quad = (tk && !strcmp(tk, "team"))   ? false
+                        : (tk && !strcmp(tk, "quad")) ? true
+                                                      : tog_plan::tail_backward(B, Bf.simds / 4) == tog_plan::TAIL_BWD_QUAD;
       if (Bf.tail && sq && TeamCfg<M>::TEAM == 16 && quad) {
         // convergence tail, square-root pass, one trajectory per workgroup: the QRs, the side work, tmp1
         // and the downdate on four waves (tog_bwd_quad.hpp)
@@ -273,6 +275,19 @@ struct ModelLaunch {
   static void forward_cand(const DevProblem* P, const DevBuffers& Bf, long long B, int mode, int bk, const double* Jp,
                            double* Jo, hipStream_t st) {
     const int F = Bf.ls_first;
+    const unsigned knots_lds = (unsigned)(Bf.nknots * (2 * sizeof(double) + sizeof(int)));
+    if (F >= Bf.nc && bk && Bf.tail) {
+      // TOG_LS_FINISH=split keeps the five launches below, for A/B checks (read per launch: tests switch it
+      // within one process)
+      const char* lf = getenv("TOG_LS_FINISH");
+      if (!(lf && !strcmp(lf, "split"))) {
+        spec<INTEG>(P, Bf, B, mode, 0, Bf.nc, nullptr, nullptr, st);
+        const unsigned rows = (mode == TOG_MODE_AL) ? (unsigned)Bf.rows_lds : 0u;
+        hipLaunchKernelGGL((k_ls_finish<M, INTEG>), dim3((unsigned)B), dim3(LS_FINISH_THREADS),
+                           knots_lds > rows ? knots_lds : rows, st, P, Bf, mode, Jp, Jo);
+        return;
+      }
+    }
     (void)hipMemsetAsync(Bf.ls_count, 0, sizeof(int) * LS_COUNT_SLOTS, st);
     if (F >= Bf.nc) {
       spec<INTEG>(P, Bf, B, mode, 0, Bf.nc, nullptr, nullptr, st);
