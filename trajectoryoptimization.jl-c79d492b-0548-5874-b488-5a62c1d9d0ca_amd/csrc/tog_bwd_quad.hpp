@@ -302,7 +302,7 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
             *(colx ? RX + j + n * tl : pad + tl) = (j <= tl) ? r[j] : 0.0;
             tag_store(&rxf[j]);
           };
-          team_qr<2 * n, n, n, TEAM, false>(a, 2 * n, tl, busA, release);
+          team_qr<2 * n, n, n, TEAM, false, true>(a, 2 * n, tl, busA, release);
 #pragma unroll
           for (int i = 0; i < n; i++) Qxc[i] = (i <= tl) ? a[i] : 0.0;
         }
@@ -691,7 +691,7 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
           *(colx ? Sreg + j + n * tl : pad + tl) = (j <= tl) ? r[j] : 0.0;
           tag_store(&rowf[j]);
         };
-        team_qr<RS, n, 0, TEAM, false>(a, RS, tl, busA, release);
+        team_qr<RS, n, 0, TEAM, false, true>(a, RS, tl, busA, release);
         if (store_S && colx) {
 #pragma unroll
           for (int i = 0; i < n; i++) Bf.Sdbg[((size_t)b * N + k) * n * n + i + n * tl] = (i <= tl) ? a[i] : 0.0;

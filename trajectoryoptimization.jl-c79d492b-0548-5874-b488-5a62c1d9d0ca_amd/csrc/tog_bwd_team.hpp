@@ -239,7 +239,12 @@ struct QrNoPost {
 };
 // POST (16-lane path): called after column step j as post(integral_constant j, a); row j of R is final
 // then (no later reflector touches it), so a consumer may take R's rows as they are released.
-template <int ROWS, int COLS, int TOP = 0, int TEAMW = 16, bool FULL = false, class POST = QrNoPost>
+// STRAIGHT (DPP paths): the second form of the column step. The reciprocal 1 / (β (α - β)) is computed on every lane
+// and selected, 0 where the sum of squares is 0 (α = 0 with ss = 0 gives an Inf that the select drops; nothing traps),
+// so the pivot's dependent run is straight-line code without the `exec` branch around the division. A live lane
+// performs the first form's operations on the same values in the same order: the bits are the same.
+template <int ROWS, int COLS, int TOP = 0, int TEAMW = 16, bool FULL = false, bool STRAIGHT = false,
+          class POST = QrNoPost>
 __device__ __forceinline__ void team_qr(double (&a)[ROWS], int rows, int tl, double* bus, const POST& post = POST{}) {
 #define TQ_LIVE(i, j) ((FULL || TEAMW == 16 || TEAMW == 4 || (i) < rows) && !((i) > (j) && (i) < TOP))
   if constexpr (TEAMW == 16 || TEAMW == 4) {
@@ -266,7 +271,13 @@ __device__ __forceinline__ void team_qr(double (&a)[ROWS], int rows, int tl, dou
       const double alpha = a[j];
       const double beta = -copysign(sqrt(fma(alpha, alpha, ss)), alpha);
       const double vd = alpha - beta;
-      const double rd = (ss != 0.0) ? 1.0 / (beta * vd) : 0.0;  // 0: tau = 0, H = I
+      double rd;  // 0: tau = 0, H = I
+      if constexpr (STRAIGHT) {
+        const double q = 1.0 / (beta * vd);
+        rd = (ss != 0.0) ? q : 0.0;
+      } else {
+        rd = (ss != 0.0) ? 1.0 / (beta * vd) : 0.0;
+      }
       if (tq == j && ss != 0.0) a[j] = beta;
       const double rdj = team_bcast<TEAMW, j>(rd), vdj = team_bcast<TEAMW, j>(vd);
       double v[ROWS];
