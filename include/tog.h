@@ -36,7 +36,8 @@ extern "C" {
 /* 5: per-trajectory linear cost terms and goals within one batch (tog_set_trajectory_costs,
       tog_set_trajectory_goals) */
 /* still 5: the streamed solves (tog_finished, tog_get_slots, tog_refill, tog_refill_tables, tog_solve_stream,
-      tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed */
+      tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed;
+      likewise tog_rollout_plan (a query for tests) */
 #define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
@@ -630,6 +631,18 @@ enum tog_kernel_id {
 int32_t tog_profile(tog_handle* h, int32_t enable);
 /* blocking: total milliseconds and launch counts per tog_kernel_id since tog_profile(h, 1) */
 int32_t tog_profile_read(tog_handle* h, double* total_ms, int64_t* launches);
+
+/* Which speculative rollout kernel a line-search launch of this handle takes now, for trials [0, cnt) of every
+   trajectory (listed = 0) or of a listed second round (listed = 1): the launch layer's own decision
+   (tog_plan::spec_kernel, csrc/tog_host_plan.hpp) on the handle's current flags, which tog_solve_step and the
+   tog_set_trajectory_* calls change. Nothing is launched. Step-level tests assert the kernel they mean to run. */
+enum tog_rollout_kernel {
+  TOG_ROLLOUT_TAIL3 = 0,  /* k_ls_spec_tail2: three waves per trajectory (convergence tail) */
+  TOG_ROLLOUT_TAIL1 = 1,  /* k_ls_spec_tail: one wave per trajectory                         */
+  TOG_ROLLOUT_BULK = 2,   /* k_ls_spec: a lane per (trajectory, trial)                       */
+  TOG_ROLLOUT_BULK_W1 = 3 /* k_ls_spec_w1: the same at one wave per SIMD                     */
+};
+int32_t tog_rollout_plan(tog_handle* h, int32_t cnt, int32_t listed, int32_t* kernel_out);
 
 /* human readable message for the last error on this thread */
 const char* tog_last_error(void);

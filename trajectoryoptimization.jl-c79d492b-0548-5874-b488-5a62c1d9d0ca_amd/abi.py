@@ -295,6 +295,8 @@ def load_library(path: os.PathLike | None = None):
     lib.tog_status.argtypes = [vp, _ip]
     lib.tog_profile.argtypes = [vp, C.c_int32]
     lib.tog_profile_read.argtypes = [vp, _dp, C.POINTER(C.c_int64)]
+    lib.tog_rollout_plan.argtypes = [vp, C.c_int32, C.c_int32, _ip]
+    lib.tog_rollout_plan.restype = C.c_int32
     lib.tog_last_error.restype = C.c_char_p
     lib.tog_dynamics_bias.argtypes = [C.c_int32, _dp, _dp]
     lib.tog_slack_controls.argtypes = [vp]
@@ -364,9 +366,12 @@ EXPORTED_SYMBOLS = (
     "tog_default_altro_options", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable", "tog_get_pn_history",
     "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs", "tog_set_trajectory_goals",
     "tog_finished", "tog_get_slots", "tog_refill", "tog_refill_tables", "tog_solve_stream", "tog_solve_stream_tables",
+    "tog_rollout_plan",
 )
 KERNEL_JACOBIAN, KERNEL_BACKWARD, KERNEL_FORWARD, KERNEL_EXPANSION = 0, 1, 2, 3
 NKERNELS = 4
+# tog_rollout_kernel (tog_rollout_plan): k_ls_spec_tail2, k_ls_spec_tail, k_ls_spec, k_ls_spec_w1
+ROLLOUT_TAIL3, ROLLOUT_TAIL1, ROLLOUT_BULK, ROLLOUT_BULK_W1 = 0, 1, 2, 3
 
 
 def check(lib, rc):

@@ -1,7 +1,10 @@
 // Host arithmetic that decides which kernel code a handle runs (tog_create): the run-time flag -> template
 // constant dispatcher of the launch table (tog_launch.hpp), the stage-cost table with its Cholesky factors and
-// diagonal-cost class, and the Q.xx pattern of the packed expansion records. Plain C++ with no device runtime in
-// it, so that a stand-alone program can run it under the host sanitizers (tests/c/host_plan_host.cpp).
+// diagonal-cost class, the Q.xx pattern of the packed expansion records, and the line search's rollout-kernel choice
+// with the LDS layout arithmetic of the tail rollouts. Plain C++ with no device runtime in it, so that a stand-alone
+// program can run it under the host sanitizers (tests/c/host_plan_host.cpp, rollout_plan_host.cpp). tog_kernels.hpp
+// includes it too: the spec_tail* constants and constexpr size functions below are the kernels' own LDS layout
+// (used in device code), so the plan and the kernels cannot disagree about it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -29,6 +32,55 @@ enum TailBackward { TAIL_BWD_TEAM = 0, TAIL_BWD_QUAD = 1 };
 constexpr long long TAIL_QUAD_ROUNDS = 1;
 inline TailBackward tail_backward(long long width, int cus) {
   return (cus > 0 && width <= TAIL_QUAD_ROUNDS * (long long)cus) ? TAIL_BWD_QUAD : TAIL_BWD_TEAM;
+}
+
+// The speculative rollout kernels of the line search (tog_kernels.hpp) and which of them a launch takes.
+// The tail kernels stage a trajectory's per-knot inputs through LDS, a chunk of spec_tail_tc knots at a time;
+// one chunk image is (doubles, field-major) [K: TC·mn | ū: TC·m | d: TC·m | x: TC·n | λ: TC·p | μ: TC·p].
+constexpr int SPEC_WAVE = 64;       // lanes of a wave: the trials of one k_ls_spec_tail workgroup
+constexpr int SPEC_TAIL_PMAX = 16;  // larger row counts per knot take k_ls_spec
+constexpr int SPEC_RQ = 4;          // k_ls_spec_tail2: steps per ring slot (and per barrier)
+constexpr int SPEC_LANES = 32;      // k_ls_spec_tail2: trials per workgroup
+constexpr int SPEC_LDS_MAX = 64 * 1024;  // dynamic LDS of a launch that raises no limit
+constexpr int spec_tail_tc(int n, int m) { return (m * n <= 64) ? 16 : 8; }
+constexpr int spec_tail_rec(int n, int m, int pmax) { return m * n + 2 * m + n + 2 * pmax; }
+// k_ls_spec_tail2's layout: two staging images (each with the terminal λ, μ after it), the ring, then SPEC_LANES
+// ints of wave A's verdicts (live_out), rounded up to whole doubles, then SPEC_LANES doubles of wave C's sums
+constexpr int spec_tail2_ring_off(int n, int m, int pmax) {
+  return 2 * (spec_tail_tc(n, m) * spec_tail_rec(n, m, pmax) + 2 * pmax);
+}
+constexpr int spec_tail2_doubles(int n, int m, int pmax) {
+  return spec_tail2_ring_off(n, m, pmax) + 2 * SPEC_RQ * (n + m) * SPEC_LANES +
+         (SPEC_LANES * (int)sizeof(int) + (int)sizeof(double) - 1) / (int)sizeof(double) + SPEC_LANES;
+}
+// LDS bytes of a tail kernel's launch for a problem of at most pmax rows per knot, 0 where the kernel is not
+// admissible: the three-wave k_ls_spec_tail2 (DevBuffers::spec_tail2_shmem) up to SPEC_TAIL_PMAX rows and within
+// SPEC_LDS_MAX, the one-wave k_ls_spec_tail (DevBuffers::spec_tail_shmem: one image) up to SPEC_TAIL_PMAX rows
+inline int spec_tail2_lds(int n, int m, int pmax) {
+  const size_t b = sizeof(double) * (size_t)spec_tail2_doubles(n, m, pmax);
+  return (pmax <= SPEC_TAIL_PMAX && b <= (size_t)SPEC_LDS_MAX) ? (int)b : 0;
+}
+inline int spec_tail_lds(int n, int m, int pmax) {
+  return pmax <= SPEC_TAIL_PMAX ? (int)(sizeof(double) * (spec_tail_tc(n, m) * spec_tail_rec(n, m, pmax) + 2 * pmax)) : 0;
+}
+// The rollout kernels that inline the diagonal cost are the shared objective's: per-trajectory costs or goals
+// (tv bit 1) ride the run-time-structure variants, and so does a dense cost (its run-time indexing of x, u would
+// put the tail kernels in scratch).
+inline bool spec_inline_diag(int cost_diag, int tv) { return cost_diag && !(tv & 2); }
+// The bulk kernel of a model with a gain block of mn entries: above 64, 64-lane workgroups at one wave per SIMD
+// (k_ls_spec_w1), which spread the waves over every CU and hold the rigid-body models' live arrays in registers
+constexpr bool spec_bulk_w1(int mn) { return mn > 64; }
+enum SpecKernel { SPEC_TAIL3 = 0, SPEC_TAIL1 = 1, SPEC_BULK = 2, SPEC_BULK_W1 = 3 };
+// The kernel of one launch of trials [lo, lo + cnt): tail, cand, cost_diag, tv as in DevBuffers; listed: a second
+// round over a device list of trajectories; tail2_lds, tail_lds: spec_tail2_lds, spec_tail_lds of the problem.
+// The tail kernels run whole rounds of the candidate-copy line search in the convergence tail: three waves up to
+// SPEC_LANES trials, one wave up to SPEC_WAVE. Everything else is the bulk kernel's.
+inline SpecKernel spec_kernel(int tail, int cand, int cost_diag, int tv, bool listed, int cnt, int tail2_lds,
+                              int tail_lds, int mn) {
+  const bool staged = tail && cand && spec_inline_diag(cost_diag, tv) && !listed;
+  if (staged && tail2_lds > 0 && cnt <= SPEC_LANES) return SPEC_TAIL3;
+  if (staged && tail_lds > 0 && cnt <= SPEC_WAVE) return SPEC_TAIL1;
+  return spec_bulk_w1(mn) ? SPEC_BULK_W1 : SPEC_BULK;
 }
 
 // upper Cholesky (dpotrf 'U') of a symmetric matrix; returns false if not PD

@@ -18,6 +18,7 @@
 #pragma once
 
 #include "tog_device.hpp"
+#include "tog_host_plan.hpp"  // the tail rollouts' LDS layout arithmetic, shared with the launch plan
 #include <string.h>
 
 namespace tog {
@@ -2274,9 +2275,11 @@ k_ls_spec_w1(const DevProblem* __restrict__ P, DevBuffers Bf, int mode, int lo, 
 // one trajectory per launch (601 µs for 100 knots). Same operations in the same order as rollout_cost
 // WMODE 3, so the trial costs, flags and candidate rollouts are bit-identical.
 // LDS image of one chunk (doubles, field-major): [K: TC·mn | ū: TC·m | d: TC·m | x: TC·n | λ: TC·p | μ: TC·p].
-__host__ __device__ constexpr int spec_tail_tc(int n, int m) { return (m * n <= 64) ? 16 : 8; }
-__host__ __device__ constexpr int spec_tail_rec(int n, int m, int pmax) { return m * n + 2 * m + n + 2 * pmax; }
-constexpr int SPEC_TAIL_PMAX = 16;  // larger row counts per knot take k_ls_spec
+// (spec_tail_tc, spec_tail_rec and SPEC_TAIL_PMAX, larger row counts per knot taking k_ls_spec: tog_host_plan.hpp)
+using tog_plan::spec_tail_tc;
+using tog_plan::spec_tail_rec;
+using tog_plan::SPEC_TAIL_PMAX;
+static_assert(tog_plan::SPEC_WAVE == WAVE, "a lane per trial of k_ls_spec_tail");
 
 template <class M, int INTEG, int DC>
 __global__ void __launch_bounds__(64) k_ls_spec_tail(const DevProblem* __restrict__ P, DevBuffers Bf, int mode,
@@ -2451,17 +2454,13 @@ __global__ void __launch_bounds__(64) k_ls_spec_tail(const DevProblem* __restric
 // costs, Jc over the row terms, J + Jc at the end), each in knot order, so splitting them between waves
 // keeps every bit. One workgroup barrier per group of SPEC_RQ steps. (With the rows on wave B as well,
 // wave A waited on B for a fifth of the rollout: profiles/r4o_trio_sections_b1.txt.)
-constexpr int SPEC_RQ = 4;      // steps per ring slot (and per barrier)
-constexpr int SPEC_LANES = 32;  // trials per workgroup
-// layout: two staging images (each with the terminal λ, μ after it), the ring, then SPEC_LANES ints of
-// wave A's verdicts (live_out), rounded up to whole doubles
-__host__ __device__ constexpr int spec_tail2_ring_off(int n, int m, int pmax) {
-  return 2 * (spec_tail_tc(n, m) * spec_tail_rec(n, m, pmax) + 2 * pmax);
-}
-__host__ __device__ constexpr int spec_tail2_doubles(int n, int m, int pmax) {
-  return spec_tail2_ring_off(n, m, pmax) + 2 * SPEC_RQ * (n + m) * SPEC_LANES +
-         (SPEC_LANES * (int)sizeof(int) + (int)sizeof(double) - 1) / (int)sizeof(double) + SPEC_LANES;
-}
+// SPEC_RQ steps per ring slot (and per barrier), SPEC_LANES trials per workgroup; layout: two staging images
+// (each with the terminal λ, μ after it), the ring, then SPEC_LANES ints of wave A's verdicts (live_out), rounded
+// up to whole doubles (spec_tail2_ring_off, spec_tail2_doubles: tog_host_plan.hpp)
+using tog_plan::SPEC_RQ;
+using tog_plan::SPEC_LANES;
+using tog_plan::spec_tail2_ring_off;
+using tog_plan::spec_tail2_doubles;
 static_assert(spec_tail2_doubles(13, 4, 13) - spec_tail2_ring_off(13, 4, 13) - 2 * SPEC_RQ * 17 * SPEC_LANES ==
                   SPEC_LANES / 2 + SPEC_LANES,
               "live_out needs SPEC_LANES ints after the ring, then SPEC_LANES doubles for wave C's Jc");

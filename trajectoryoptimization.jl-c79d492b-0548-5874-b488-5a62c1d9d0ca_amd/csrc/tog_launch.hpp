@@ -236,17 +236,18 @@ struct ModelLaunch {
   template <int INTEG>
   static void spec(const DevProblem* P, const DevBuffers& Bf, long long B, int mode, int lo, int cnt, const int* list,
                    const int* count, hipStream_t st) {
-    // the tail kernels inline the diagonal cost only (the dense cost's run-time indexing of x, u would put
-    // them in scratch); dense costs take k_ls_spec
-    // (per-trajectory costs or goals, Bf.tv bit 1, ride the run-time-structure variants, DC = 0: the kernels that
-    // inline the diagonal cost are the shared objective's and keep their code)
-    const bool diag = Bf.cost_diag && !(Bf.tv & 2);
-    if (Bf.tail && Bf.cand && Bf.spec_tail2_shmem > 0 && diag && !list && cnt <= SPEC_LANES) {
+    // which kernel: tog_plan::spec_kernel (the tail kernels inline the diagonal cost only, DC = 1; dense costs and
+    // per-trajectory cost data take k_ls_spec's run-time-structure variants, DC = 0)
+    const bool diag = tog_plan::spec_inline_diag(Bf.cost_diag, Bf.tv);
+    const tog_plan::SpecKernel kern =
+        tog_plan::spec_kernel(Bf.tail, Bf.cand ? 1 : 0, Bf.cost_diag, Bf.tv, list != nullptr, cnt,
+                              Bf.spec_tail2_shmem, Bf.spec_tail_shmem, M::n * M::m);
+    if (kern == tog_plan::SPEC_TAIL3) {
       hipLaunchKernelGGL((k_ls_spec_tail2<M, INTEG, 1>), dim3((unsigned)B), dim3(3 * WAVE),
                          (unsigned)Bf.spec_tail2_shmem, st, P, Bf, mode, lo, cnt);
       return;
     }
-    if (Bf.tail && Bf.cand && Bf.spec_tail_shmem > 0 && diag && !list && cnt <= WAVE) {
+    if (kern == tog_plan::SPEC_TAIL1) {
       hipLaunchKernelGGL((k_ls_spec_tail<M, INTEG, 1>), dim3((unsigned)B), dim3(WAVE), (unsigned)Bf.spec_tail_shmem, st,
                          P, Bf, mode, lo, cnt);
       return;
@@ -259,7 +260,8 @@ struct ModelLaunch {
           constexpr bool CAND = decltype(cand_c)::value != 0, LRT = decltype(lrt_c)::value != 0;
           // (the candidate-copy line search is the default path: only its kernels know the diagonal cost)
           constexpr int DC = CAND ? decltype(diag_c)::value : 0;
-          if constexpr (M::n * M::m > 64)  // (64-lane workgroups spread the waves over every CU: 5% on the Kuka's)
+          // SPEC_BULK_W1 (64-lane workgroups spread the waves over every CU: 5% on the Kuka's) or SPEC_BULK
+          if constexpr (tog_plan::spec_bulk_w1(M::n * M::m))
             hipLaunchKernelGGL((k_ls_spec_w1<M, INTEG, CAND, LRT, DC>), dim3(grid(B * (long long)cnt, 64)), dim3(64),
                                LRT ? rb : 0u, st, P, Bf, mode, lo, cnt, list, count);
           else

@@ -1061,15 +1061,10 @@ static bool choose_variants(tog_handle* h, const tog_problem_desc* d, const tog_
   }
   // bulk k_ls_spec: a block's LDS copy of the row tables
   b.rows_lds = row_tables_bytes(nrows, N);
-  // the tail rollouts staged through LDS, admissible up to SPEC_TAIL_PMAX rows per knot: k_ls_spec_tail2 (two
+  // the tail rollouts staged through LDS, admissible up to SPEC_TAIL_PMAX rows per knot: k_ls_spec_tail2 (three
   // waves) within 64 KB of LDS, else the one-wave k_ls_spec_tail
-  {
-    const size_t b2 = sizeof(double) * (size_t)spec_tail2_doubles(n, m, h->pmax);
-    b.spec_tail2_shmem = (h->pmax <= SPEC_TAIL_PMAX && b2 <= 64 * 1024) ? (int)b2 : 0;
-  }
-  b.spec_tail_shmem = h->pmax <= SPEC_TAIL_PMAX
-                          ? (int)(sizeof(double) * (spec_tail_tc(n, m) * spec_tail_rec(n, m, h->pmax) + 2 * h->pmax))
-                          : 0;
+  b.spec_tail2_shmem = tog_plan::spec_tail2_lds(n, m, h->pmax);
+  b.spec_tail_shmem = tog_plan::spec_tail_lds(n, m, h->pmax);
   b.tv = d->stage_costs ? 1 : 0;
   h->tv0 = b.tv;
   b.dense_stage_knots = 0;  // a stage knot with a state row (its square-root expansion changes Q.xx)
@@ -2370,6 +2365,22 @@ int32_t tog_solve_stream_tables(tog_handle* h, int32_t mode, int64_t njobs, cons
     return fail(TOG_ERR_ARG, "tog_solve_stream_tables: every table the handle has needs the jobs' rows");
   return solve_stream(h, mode, njobs, x0, U0, lin, term, xf, X_out, U_out, stats_out, max_steps, jobs_done,
                       "tog_solve_stream_tables");
+}
+
+static_assert((int)TOG_ROLLOUT_TAIL3 == (int)tog_plan::SPEC_TAIL3 && (int)TOG_ROLLOUT_TAIL1 == (int)tog_plan::SPEC_TAIL1 &&
+                  (int)TOG_ROLLOUT_BULK == (int)tog_plan::SPEC_BULK &&
+                  (int)TOG_ROLLOUT_BULK_W1 == (int)tog_plan::SPEC_BULK_W1,
+              "tog_rollout_kernel mirrors tog_plan::SpecKernel");
+
+int32_t tog_rollout_plan(tog_handle* h, int32_t cnt, int32_t listed, int32_t* kernel_out) {
+  if (!h || !kernel_out) return fail(TOG_ERR_ARG, "null argument");
+  if (is_multi(h)) return tog_rollout_plan(h->parts[0], cnt, listed, kernel_out);  // (the parts share their flags)
+  const DevBuffers& b = h->buf;
+  if (cnt < 1 || cnt > b.nc) return fail(TOG_ERR_ARG, "tog_rollout_plan: cnt outside [1, iterations_linesearch + 1]");
+  // the arguments ModelLaunch::spec passes (tog_launch.hpp)
+  *kernel_out = (int32_t)tog_plan::spec_kernel(b.tail, b.cand ? 1 : 0, b.cost_diag, b.tv, listed != 0, cnt,
+                                                b.spec_tail2_shmem, b.spec_tail_shmem, h->ops->n * h->ops->m);
+  return TOG_OK;
 }
 
 int32_t tog_profile(tog_handle* h, int32_t enable) {

@@ -328,6 +328,15 @@ class BatchHandle:
         abi.check(self.lib, self.lib.tog_profile_read(self.h, abi.as_dp(ms), cnt))
         return ms, np.array(list(cnt), dtype=np.int64)
 
+    def rollout_plan(self, cnt=None, listed=False):
+        """tog_rollout_plan: the rollout kernel (abi.ROLLOUT_*) a line-search launch of trials [0, cnt) takes on the
+        handle's current flags; cnt None: every trial (iterations_linesearch + 1)."""
+        if cnt is None:
+            cnt = min(int(self.opts.iterations_linesearch) + 1, 64)
+        k = C.c_int32()
+        abi.check(self.lib, self.lib.tog_rollout_plan(self.h, int(cnt), int(bool(listed)), C.byref(k)))
+        return int(k.value)
+
     def synchronize(self):
         abi.check(self.lib, self.lib.tog_synchronize(self.h))
 
