@@ -37,7 +37,8 @@ extern "C" {
       tog_set_trajectory_goals) */
 /* still 5: the streamed solves (tog_finished, tog_get_slots, tog_refill, tog_refill_tables, tog_solve_stream,
       tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed;
-      likewise tog_rollout_plan (a query for tests) */
+      likewise tog_rollout_plan (a query for tests) and tog_set_trajectory_obstacles (per-trajectory circle and
+      sphere data) */
 #define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
@@ -166,9 +167,11 @@ typedef struct tog_constraint_set {
    (src/cost.jl:112-157, src/objective.jl:102-114) and per-knot constraint sets
    (src/constraint_sets.jl:157-206). One problem, B independent trajectories
    that differ in x0 and the initial controls U0 and, once set on the handle, in the
-   linear and constant terms of their cost and in their goal
-   (tog_set_trajectory_costs, tog_set_trajectory_goals). The cost Hessians, the
-   dynamics and every other constraint are the batch's. */
+   linear and constant terms of their cost, in their goal and in the centres and radii
+   of their circle and sphere obstacles (tog_set_trajectory_costs,
+   tog_set_trajectory_goals, tog_set_trajectory_obstacles). The cost Hessians, the
+   dynamics, the bounds, the user constraints and the number and kind of the obstacles
+   are the batch's. */
 typedef struct tog_problem_desc {
   int32_t model;      /* tog_model_id                       */
   int32_t integrator; /* tog_integrator                     */
@@ -389,6 +392,17 @@ int32_t tog_set_trajectory_costs(tog_handle* h, int32_t per_knot, const double* 
    TOG_ERR_ARG when the problem has no goal constraint; TOG_ERR_UNSUPPORTED when a goal row sits at a stage
    knot or two terminal goal rows constrain one state, and in the cases named above. */
 int32_t tog_set_trajectory_goals(tog_handle* h, const double* xf);
+/* Per-trajectory obstacles: the data of the TOG_CON_CIRCLES / TOG_CON_SPHERES rows. obs: (4, no, B), host
+   pointer; entry (., j, b) is [x0, y0, 0, r] of a circle, [x0, y0, z0, r] of a sphere, for trajectory b. no
+   counts the obstacles of every circles / spheres constraint in desc.sets[], and j is the obstacle's ordinal in
+   that order: sets in order, constraints in their set's order, obstacles in their constraint's order. A set
+   used at many knots contributes once; the data are the same at every knot (no moving obstacles). NULL restores
+   the descriptor's values. Replacement, lifetime and the split on a tog_create_multi handle are as for
+   tog_set_trajectory_costs. TOG_ERR_ARG when the problem has no circle or sphere constraint;
+   TOG_ERR_UNSUPPORTED on a TOG_PROB_INFEASIBLE or TOG_PROB_MIN_TIME handle. While the table is set,
+   tog_solve_pn, tog_refill, tog_refill_tables, tog_solve_stream and tog_solve_stream_tables return
+   TOG_ERR_UNSUPPORTED (they would read the descriptor's obstacles). */
+int32_t tog_set_trajectory_obstacles(tog_handle* h, const double* obs);
 /* copy a field host->device / device->host (host pointers, sizes per tog_field) */
 int32_t tog_set(tog_handle* h, int32_t field, const double* in);
 int32_t tog_get(tog_handle* h, int32_t field, double* out);

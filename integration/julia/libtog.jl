@@ -491,6 +491,22 @@ function tog_set_trajectory_goals!(s::BatchediLQRSolver, xf::Union{Nothing,Matri
 end
 
 """
+    tog_set_trajectory_obstacles!(solver, obs)
+
+Per-trajectory circle and sphere data (include/tog.h). `obs` is `(4, no, B)`: entry `[:, j, b]` is `[x0, y0, 0, r]`
+of a circle or `[x0, y0, z0, r]` of a sphere for trajectory `b`; `j` runs over the obstacles of every circles /
+spheres constraint of the problem's sets, in set order, then constraint order, then the constraint's own order.
+`nothing` restores the problem's values. Infeasible-start and minimum-time solvers refuse it; while it is set,
+projected Newton and the streamed solves are refused.
+"""
+function tog_set_trajectory_obstacles!(s::BatchediLQRSolver, obs::Union{Nothing,Array{Float64,3}})
+    obs === nothing || (size(obs, 1) == 4 && size(obs, 3) == s.B) || throw(ArgumentError("obs must be (4, no, B)"))
+    togcheck(ccall((:tog_set_trajectory_obstacles, libtog), Int32, (Ptr{Cvoid}, Ptr{Float64}),
+                   s.handle, obs === nothing ? C_NULL : obs))
+    return nothing
+end
+
+"""
     tog_finished(solver) -> Vector{Int32}
     tog_get_slots(solver, field, slots, width) -> Matrix{Float64}   # width: the field's doubles per trajectory
     tog_refill!(solver, slots, x0, U, X = nothing)

@@ -102,6 +102,11 @@ struct DevProblem {
   const double* term;
   const double* goal;
   int lin_per_knot, goal_ld;
+  // Per-trajectory obstacles (tog_set_trajectory_obstacles; null: the rows' own data): [x0, y0, z0, r] of every
+  // circle and sphere, laid out (4, no, B), indexed by a ROW_CIRCLE / ROW_SPHERE row's obstacle ordinal (its idx).
+  // obs_ld = 4 no doubles per trajectory; each entry is 32 bytes and 32-byte aligned.
+  const double* obs;
+  int obs_ld, obs_pad;
 };
 
 // Read-only device tables seen through the constant address space. The row tables are read at the
@@ -197,8 +202,8 @@ struct DevBuffers {
   int spec_tail2_shmem; // LDS bytes of k_ls_spec_tail2 (two staging images + the ring; 0: not admissible)
   int cost_diag;       // DevProblem::diag_cost (host copy: kernel variants that inline the diagonal cost)
   int tv;              // bit 0: a per-knot cost table (DevProblem::kc: a time-varying Objective, or per-trajectory
-                       // data beside the replicated shared cost): the team backward kernels' per-knot-cost variants;
-                       // bit 1: per-trajectory costs or goals (DevProblem::lin, term, goal): the PT variants of
+                       // cost data beside the replicated shared cost): the team backward kernels' per-knot-cost variants;
+                       // bit 1: per-trajectory costs, goals or obstacles (DevProblem::lin, term, goal, obs): the PT variants of
                        // the expansion kernels, and the rollouts' run-time-structure (DC = 0) variants
   int rows_lds;        // LDS bytes of a block's copy of the row tables (bulk k_ls_spec; 0: global tables)
   int ls_first;       // width of the first speculative round (>= nc: one round)
@@ -1362,11 +1367,21 @@ __device__ __forceinline__ TermView term_at(const DevProblem* P, long long b) {
   return TermView{P->qf, P->cf};
 }
 // A loaded constraint row as trajectory b sees it: a goal row takes its target from the goal table
-// (DevProblem::goal). Applied after the row is loaded (from the global tables or an LDS copy of them) and after
-// uniform_row: a is per lane, never wave-uniform (the team kernels hold several trajectories in a wave).
+// (DevProblem::goal), a circle or sphere row its centre and radius from the obstacle table (DevProblem::obs, one
+// 32-byte entry at the row's ordinal). Applied after the row is loaded (from the global tables or an LDS copy of
+// them) and after uniform_row: type and idx are wave-uniform there, the data are per lane, never wave-uniform
+// (the team kernels hold several trajectories in a wave).
+typedef double obs_entry __attribute__((ext_vector_type(4)));  // [x0, y0, z0, r]
 template <bool PT = true>
 __device__ __forceinline__ ConRow traj_row(const DevProblem* P, long long b, ConRow r) {
   if (PT && r.type == ROW_GOAL && P->goal) r.a = as_global(P->goal)[(size_t)b * P->goal_ld + r.idx];
+  if (PT && (r.type == ROW_CIRCLE || r.type == ROW_SPHERE) && P->obs) {
+    const obs_entry e = as_global((const obs_entry*)P->obs)[(size_t)b * (P->obs_ld >> 2) + r.idx];
+    r.a = e.x;
+    r.b = e.y;
+    r.c = e.z;
+    r.r = e.w;
+  }
   return r;
 }
 

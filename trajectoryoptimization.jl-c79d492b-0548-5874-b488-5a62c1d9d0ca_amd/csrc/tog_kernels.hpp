@@ -952,9 +952,10 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
   }
   wsync();
   for (int r = lane; r < p; r += WAVE) {  // p may exceed the wave (PCAP > 64)
-    const double c = row_value_m<M>(traj_row(P, b, rows[r]), sh.xk, term ? nullptr : sh.uk);
+    const ConRow row = traj_row(P, b, rows[r]);  // (the gradient of a circle or sphere row reads its data too)
+    const double c = row_value_m<M>(row, sh.xk, term ? nullptr : sh.uk);
     const double l = lam[r];
-    const bool a = row_inequality(rows[r]) ? ((c >= 0.0) || (l > 0.0)) : true;
+    const bool a = row_inequality(row) ? ((c >= 0.0) || (l > 0.0)) : true;
     const double w = a ? mu[r] : 0.0;
     sh.cval[r] = c;
     sh.wv[r] = w;
@@ -962,7 +963,7 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
     sh.gv[r] = w * c + l;
     int idx[row_grad_cap<M>()];
     double v[row_grad_cap<M>()];
-    const int nz = row_grad_m<M>(rows[r], sh.xk, term ? nullptr : sh.uk, idx, v);
+    const int nz = row_grad_m<M>(row, sh.xk, term ? nullptr : sh.uk, idx, v);
     for (int z = 0; z < nz; z++) {
       if (idx[z] < n)
         sh.cx[r + p * idx[z]] = v[z];
@@ -3502,7 +3503,7 @@ __global__ void __launch_bounds__(64) k_cost_expansion(const DevProblem* __restr
   for (int i = 0; i < p * n; i++) cx[i] = 0.0;
   for (int i = 0; i < p * m; i++) cu[i] = 0.0;
   for (int r = 0; r < p; r++) {
-    const ConRow row = rows[r];
+    const ConRow row = traj_row(P, b, rows[r]);
     int idx[row_grad_cap<M>()];
     double v[row_grad_cap<M>()];
     const int nz = row_grad_m<M>(row, x, u, idx, v);

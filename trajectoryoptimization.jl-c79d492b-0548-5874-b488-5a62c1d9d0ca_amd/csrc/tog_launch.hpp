@@ -13,11 +13,12 @@ using tog_plan::pick;
 // The kernels' ALI template argument from the run-time flags: bit 0 the augmented-Lagrangian terms (al), bit 1
 // a variant that reads cost data from tables (DevBuffers::tv). The two kernel families key bit 1 differently.
 // The team and quad backward kernels read the shared Hessians from DevProblem unless bit 1 is set, so they need
-// it whenever there is a per-knot table (any bit of tv: a time-varying Objective, or per-trajectory data beside
-// the replicated shared cost).
-inline int ali_backward(int al, int tv) { return (al ? 1 : 0) | (tv ? 2 : 0); }
+// it whenever there is a per-knot table (tv bit 0: a time-varying Objective, or per-trajectory cost data beside
+// the replicated shared cost). They read no constraint row: a handle whose only table is the obstacles' (tv = 2)
+// keeps the shared-cost variants.
+inline int ali_backward(int al, int tv) { return (al ? 1 : 0) | ((tv & 1) ? 2 : 0); }
 // The expansion kernels look for the per-knot table at run time in every variant (cost_at), so their extra
-// variants are only the per-trajectory ones (tv bit 1: DevProblem::lin, term, goal).
+// variants are only the per-trajectory ones (tv bit 1: DevProblem::lin, term, goal, obs).
 inline int ali_expand(int al, int tv) { return (al ? 1 : 0) | ((tv & 2) ? 2 : 0); }
 
 // a second stream on the handle's device and the fork/join events that overlap work on it

@@ -149,6 +149,10 @@ struct tog_handle {
   std::vector<double> kc_row;
   std::vector<int> goal_idx;  // state index of each terminal goal row, in row order (ng = size)
   std::string goal_err;       // why the problem's goal rows cannot vary per trajectory (empty: they can)
+  // per-trajectory obstacles (tog_set_trajectory_obstacles; DevProblem::obs): the device table (4, no, B), and
+  // circle (0) or sphere (1) of each obstacle ordinal of the descriptor's sets table (no = size)
+  double* d_obs = nullptr;
+  std::vector<char> obs_kind;
   // Streamed solves (tog_finished / tog_get_slots / tog_refill / tog_solve_stream), allocated on first use and
   // freed in tog_destroy; everything is ordered on the handle's stream.
   // d_slot_job (B): the job a slot holds whose end has not been listed yet (-1: empty, or listed by
@@ -239,11 +243,28 @@ static const ModelOps* ops_for(int model, bool infeasible, bool min_time, const 
 
 // Flatten the ordered constraint sets into per-knot rows (src/constraint_sets.jl:64-131).
 static int build_rows(const tog_problem_desc* d, int slack, int pcap, int has_con, std::vector<ConRow>& rows,
-                      std::vector<int>& off, std::vector<int>& cnt) {
+                      std::vector<int>& off, std::vector<int>& cnt, std::vector<char>* obs_kind = nullptr) {
   const int n = d->n, m = d->m, N = d->N;
   const int mt = (d->flags & TOG_PROB_MIN_TIME) ? 1 : 0;  // h, the last control
   off.assign(N, 0);
   cnt.assign(N, 0);
+  // the ordinal of every circle and sphere (tog_set_trajectory_obstacles' table index, kept in ConRow::idx)
+  std::vector<int> set_first(d->n_sets > 0 ? d->n_sets : 0, 0), obs_base;
+  {
+    std::vector<int> ncon, ctype, ccount;
+    for (int s = 0; s < d->n_sets; s++) {
+      set_first[s] = (int)ctype.size();
+      ncon.push_back(d->sets[s].n_con);
+      for (int c = 0; c < d->sets[s].n_con; c++) {
+        ctype.push_back(d->sets[s].con[c].type);
+        ccount.push_back(d->sets[s].con[c].count);
+      }
+    }
+    std::vector<char> kind;
+    tog_traj::obstacle_ordinals(ncon.data(), d->n_sets, ctype.data(), ccount.data(), TOG_CON_CIRCLES, TOG_CON_SPHERES,
+                                obs_base, kind);
+    if (obs_kind) *obs_kind = kind;
+  }
   for (int k = 0; k < N; k++) {
     off[k] = (int)rows.size();
     const int si = d->knot_set ? d->knot_set[k] : -1;
@@ -288,12 +309,12 @@ static int build_rows(const tog_problem_desc* d, int slack, int pcap, int has_co
         case TOG_CON_CIRCLES:
           if (!term)
             for (int o = 0; o < con.count; o++)
-              rows.push_back({ROW_CIRCLE, 0, D[3 * o], D[3 * o + 1], 0.0, D[3 * o + 2]});
+              rows.push_back({ROW_CIRCLE, obs_base[set_first[si] + c] + o, D[3 * o], D[3 * o + 1], 0.0, D[3 * o + 2]});
           break;
         case TOG_CON_SPHERES:
           if (!term)
             for (int o = 0; o < con.count; o++)
-              rows.push_back({ROW_SPHERE, 0, D[4 * o], D[4 * o + 1], D[4 * o + 2], D[4 * o + 3]});
+              rows.push_back({ROW_SPHERE, obs_base[set_first[si] + c] + o, D[4 * o], D[4 * o + 1], D[4 * o + 2], D[4 * o + 3]});
           break;
         case TOG_CON_INFEASIBLE:
           // infeasible_constraints(n, m) (src/constraints.jl:306-314): c = u[m+1:m+n], stage only
@@ -1185,7 +1206,7 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
   h->nq = n + m + n * n + m * m + m * n;
 
   HostRows hr;
-  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, hr.rows, hr.off, hr.cnt);
+  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, hr.rows, hr.off, hr.cnt, &h->obs_kind);
   if (rc) return rc;
   h->nrows = (int)hr.rows.size();
   h->pmax = 0;
@@ -1543,19 +1564,23 @@ int32_t tog_set_state(tog_handle* h, const double* x0, const double* U, const do
 // beside (the descriptor's, or N - 1 copies of its one stage cost), the table pointers, the kernel variant flag
 static int32_t traj_apply(tog_handle* h) {
   DevProblem& P = h->hostP;
-  const bool any = h->d_lin || h->d_term || h->d_goal;
-  if (any && !h->kc0 && !h->d_kc_rep) {
+  // (the obstacle table needs no per-knot cost table: cost_at returns the shared cost without one, and the
+  // backward kernels read no constraint row, so an obstacle-only handle sets variant bit 1 alone)
+  const bool cost = h->d_lin || h->d_term || h->d_goal, any = cost || h->d_obs;
+  if (cost && !h->kc0 && !h->d_kc_rep) {
     const std::vector<double> t = tog_traj::replicate_row(h->kc_row, h->N - 1);
     int32_t rc = dalloc(h, &h->d_kc_rep, t.size());
     if (rc) return rc;
     HIPCHECK(hipMemcpy(h->d_kc_rep, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
   }
-  P.kc = h->kc0 ? h->kc0 : (any ? h->d_kc_rep : nullptr);
+  P.kc = h->kc0 ? h->kc0 : (cost ? h->d_kc_rep : nullptr);
   P.lin = h->d_lin;
   P.term = h->d_term;
   P.goal = h->d_goal;
   P.goal_ld = h->n;
-  h->buf.tv = ((h->tv0 || any) ? 1 : 0) | (any ? 2 : 0);  // (bit 1: the per-trajectory kernel variants)
+  P.obs = h->d_obs;
+  P.obs_ld = (int)tog_traj::obs_width((int)h->obs_kind.size());
+  h->buf.tv = ((h->tv0 || cost) ? 1 : 0) | (any ? 2 : 0);  // (bit 1: the per-trajectory kernel variants)
   HIPCHECK(hipStreamSynchronize(h->stream));
   HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
   return TOG_OK;
@@ -1629,6 +1654,28 @@ int32_t tog_set_trajectory_goals(tog_handle* h, const double* xf) {
     rc = traj_table(h, &h->d_goal, t.data(), t.size());
   } else {
     rc = traj_table(h, &h->d_goal, nullptr, 0);
+  }
+  const int32_t ra = traj_apply(h);
+  return rc ? rc : ra;
+}
+
+int32_t tog_set_trajectory_obstacles(tog_handle* h, const double* obs) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (is_multi(h)) {
+    const size_t w = tog_traj::obs_width((int)h->parts[0]->obs_kind.size());
+    return each_part(h, [&](tog_handle* p, size_t o) {
+      return tog_set_trajectory_obstacles(p, tog_traj::part_slice(obs, o, w));
+    });
+  }
+  if (h->ops->slack || h->ops->min_time) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_refuse_text());
+  if (h->obs_kind.empty()) return fail(TOG_ERR_ARG, tog_traj::obstacles_none_text());
+  HIPCHECK(hipSetDevice(h->device));
+  int32_t rc;
+  if (obs) {
+    const std::vector<double> t = tog_traj::obstacle_table(obs, h->obs_kind, h->B);
+    rc = traj_table(h, &h->d_obs, t.data(), t.size());
+  } else {
+    rc = traj_table(h, &h->d_obs, nullptr, 0);
   }
   const int32_t ra = traj_apply(h);
   return rc ? rc : ra;
@@ -1971,6 +2018,13 @@ static int32_t stream_refuse(const tog_handle* h, const char* who) {
   return TOG_OK;
 }
 
+// while the obstacle table is set: the refill staging carries no obstacle rows, so a refilled slot would keep the
+// last job's obstacles (streaming obstacle sweeps is not built)
+static int32_t obs_refuse(const tog_handle* h, const char* who) {
+  if (h && !is_multi(h) && h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text(who));
+  return TOG_OK;
+}
+
 // first use: the slot arrays, their pinned images and the events
 static int32_t stream_alloc(tog_handle* h) {
   if (h->d_slot_job) return TOG_OK;
@@ -2299,7 +2353,7 @@ int32_t tog_get_slots(tog_handle* h, int32_t field, int32_t count, const int32_t
 
 int32_t tog_refill(tog_handle* h, int32_t count, const int32_t* slots, const double* x0, const double* U, const double* X) {
   int32_t rc = stream_refuse(h, "tog_refill");
-  if (rc) return rc;
+  if (rc || (rc = obs_refuse(h, "tog_refill"))) return rc;
   if ((rc = check_slots(h, count, slots, true, "tog_refill"))) return rc;
   if (count == 0) return TOG_OK;
   if (!x0 || !U) return fail(TOG_ERR_ARG, "null argument");
@@ -2326,7 +2380,7 @@ int32_t tog_refill(tog_handle* h, int32_t count, const int32_t* slots, const dou
 int32_t tog_refill_tables(tog_handle* h, int32_t count, const int32_t* slots, const double* lin, const double* term,
                           const double* xf) {
   int32_t rc = stream_refuse(h, "tog_refill_tables");
-  if (rc) return rc;
+  if (rc || (rc = obs_refuse(h, "tog_refill_tables"))) return rc;
   if ((rc = tables_check(h, lin, term, xf, "tog_refill_tables"))) return rc;
   if ((rc = check_slots(h, count, slots, true, "tog_refill_tables"))) return rc;
   if (count == 0 || (!lin && !term && !xf)) return TOG_OK;
@@ -2344,6 +2398,7 @@ int32_t tog_refill_tables(tog_handle* h, int32_t count, const int32_t* slots, co
 
 int32_t tog_solve_stream(tog_handle* h, int32_t mode, int64_t njobs, const double* x0, const double* U0, double* X_out,
                          double* U_out, double* stats_out, int32_t max_steps, int64_t* jobs_done) {
+  if (int32_t rc = obs_refuse(h, "tog_solve_stream")) return rc;
   if (h && !is_multi(h) && (h->d_lin || h->d_term || h->d_goal))
     return fail(TOG_ERR_ARG, "tog_solve_stream: the handle has per-trajectory cost or goal tables; give every job its "
                              "rows through tog_solve_stream_tables");
@@ -2355,7 +2410,7 @@ int32_t tog_solve_stream_tables(tog_handle* h, int32_t mode, int64_t njobs, cons
                                 const double* lin, const double* term, const double* xf, double* X_out, double* U_out,
                                 double* stats_out, int32_t max_steps, int64_t* jobs_done) {
   int32_t rc = stream_refuse(h, "tog_solve_stream_tables");
-  if (rc) return rc;
+  if (rc || (rc = obs_refuse(h, "tog_solve_stream_tables"))) return rc;
   if (!h->d_lin && !h->d_term && !h->d_goal)
     return fail(TOG_ERR_UNSUPPORTED, "tog_solve_stream_tables: the handle has no per-trajectory table (set them with "
                                      "tog_set_trajectory_costs / tog_set_trajectory_goals first; their kernel "
@@ -2447,6 +2502,7 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
   if (h->d_lin || h->d_term || h->d_goal)
     return fail(TOG_ERR_UNSUPPORTED, "tog_solve_pn: per-trajectory costs or goals are set (projected Newton reads the "
                                      "shared objective and goal; clear them with NULL tables first)");
+  if (h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text("tog_solve_pn"));
   const bool optimal = opts->solve_type == 1;
   if (opts->n_steps < 0) return fail(TOG_ERR_ARG, "n_steps must be >= 0");
   if (!h->ops->pn) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");

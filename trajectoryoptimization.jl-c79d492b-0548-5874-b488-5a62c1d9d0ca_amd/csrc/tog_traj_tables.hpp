@@ -56,6 +56,53 @@ inline std::vector<double> replicate_row(const std::vector<double>& row, int kno
   return t;
 }
 
+// ---- per-trajectory obstacles (tog_set_trajectory_obstacles): the data of the circle and sphere rows.
+// Every obstacle of every circles / spheres constraint in the descriptor's sets table has an ordinal: sets in
+// order, constraints in their set's order, obstacles in their constraint's order. A set used at many knots (or at
+// none) contributes once. set_ncon[s]: constraints of set s; con_type / con_count: type and obstacle count of
+// each constraint, all sets' constraints in one run. base[i]: the ordinal of constraint i's first obstacle (-1:
+// not an obstacle constraint); kind[j]: 0 for a circle, 1 for a sphere. Returns no, the number of ordinals.
+inline int obstacle_ordinals(const int* set_ncon, int n_sets, const int* con_type, const int* con_count,
+                             int circles_type, int spheres_type, std::vector<int>& base, std::vector<char>& kind) {
+  base.clear();
+  kind.clear();
+  int i = 0, no = 0;
+  for (int s = 0; s < n_sets; s++)
+    for (int c = 0; c < set_ncon[s]; c++, i++) {
+      const bool obs = con_type[i] == circles_type || con_type[i] == spheres_type;
+      const int cnt = obs && con_count[i] > 0 ? con_count[i] : 0;
+      base.push_back(obs ? no : -1);
+      kind.insert(kind.end(), (size_t)cnt, con_type[i] == spheres_type ? 1 : 0);
+      no += cnt;
+    }
+  return no;
+}
+// doubles per trajectory of the obstacle array, and of the device table (DevProblem::obs_ld)
+inline size_t obs_width(int no) { return 4 * (size_t)no; }
+// (4, no, B) -> the device table's host image, the same layout: entry (., j, b) = [x0, y0, z0, r], with the
+// unused third number of a circle stored as 0
+inline std::vector<double> obstacle_table(const double* obs, const std::vector<char>& kind, long long B) {
+  const size_t no = kind.size();
+  std::vector<double> t(obs, obs + obs_width((int)no) * (size_t)B);
+  for (long long b = 0; b < B; b++)
+    for (size_t j = 0; j < no; j++)
+      if (!kind[j]) t[((size_t)b * no + j) * 4 + 2] = 0.0;
+  return t;
+}
+inline std::string obstacles_none_text() {
+  return "tog_set_trajectory_obstacles: the problem has no circle or sphere constraint";
+}
+// infeasible-start and minimum-time handles
+inline std::string obstacles_refuse_text() {
+  return "tog_set_trajectory_obstacles: infeasible-start and minimum-time problems keep the batch's obstacles "
+         "(their augmented rows are built from the descriptor)";
+}
+// the entry points whose kernels or staging read the descriptor's obstacle data
+inline std::string obstacles_set_text(const char* who) {
+  return std::string(who) + ": per-trajectory obstacles are set (this call reads the descriptor's circle and sphere "
+                            "data; clear the table with tog_set_trajectory_obstacles(h, NULL) first)";
+}
+
 // a host array's slice for the part of a multi-device handle that starts at trajectory `off` (the batch axis is
 // the outermost one; a null array stays null)
 inline const double* part_slice(const double* a, size_t off, size_t width) { return a ? a + off * width : nullptr; }

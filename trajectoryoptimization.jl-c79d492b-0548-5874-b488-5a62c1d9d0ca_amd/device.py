@@ -118,6 +118,11 @@ class BatchHandle:
             self.set_trajectory_goals(goals)
         elif getattr(self, "_traj_goals", False):
             self.set_trajectory_goals(None)
+        obs = prob.trajectory_obstacles() if hasattr(prob, "trajectory_obstacles") else None
+        if obs is not None:
+            self.set_trajectory_obstacles(obs)
+        elif getattr(self, "_traj_obstacles", False):
+            self.set_trajectory_obstacles(None)
 
     def set_trajectory_costs(self, lin=None, term=None):
         """tog_set_trajectory_costs. lin: (B, n+m+1) rows [q; r; c], or (B, N-1, n+m+1) with a row per stage
@@ -151,6 +156,19 @@ class BatchHandle:
             raise ValueError(f"xf must be ({self.B}, ng), got {xf.shape}")
         abi.check(self.lib, self.lib.tog_set_trajectory_goals(self.h, abi.as_dp(xf)))
         self._traj_goals = True
+
+    def set_trajectory_obstacles(self, obs=None):
+        """tog_set_trajectory_obstacles. obs: (B, no, 4) rows [x0, y0, z0, r] of every circle and sphere in the
+        ABI's ordinal order (Problem.trajectory_obstacles); None: the descriptor's."""
+        if obs is None:
+            abi.check(self.lib, self.lib.tog_set_trajectory_obstacles(self.h, C.cast(None, C.POINTER(C.c_double))))
+            self._traj_obstacles = False
+            return
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 3 or obs.shape[0] != self.B or obs.shape[2] != 4:
+            raise ValueError(f"obs must be ({self.B}, no, 4), got {obs.shape}")
+        abi.check(self.lib, self.lib.tog_set_trajectory_obstacles(self.h, abi.as_dp(obs)))
+        self._traj_obstacles = True
 
     def download_state(self, prob):
         prob._X[...] = self.get(abi.FIELD_X)

@@ -778,48 +778,100 @@ def sphere_constraint(x, x0, y0, z0=None, r=None):
     return -((x[0] - x0) ** 2 + (x[1] - y0) ** 2 + (x[2] - z0) ** 2 - r ** 2)
 
 
+def _obstacle_array(a, w, who):
+    """(no, w), or (B, no, w) with an obstacle set per trajectory (tog_set_trajectory_obstacles)"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 3:
+        if a.shape[2] != w:
+            raise ValueError(f"{who}: per-trajectory data must be (B, no, {w}), got {a.shape}")
+        return a.copy()
+    return a.reshape(-1, w).copy()
+
+
 class CircleConstraints(_Constraint):
     """A ``Constraint{Inequality}`` whose rows are ``circle_constraint(x, xc, yc, r)`` — the
-    reference's cylinder-obstacle idiom (problems/quad_obs.jl:53-62). Stage only."""
+    reference's cylinder-obstacle idiom (problems/quad_obs.jl:53-62). Stage only. ``circles`` is (no, 3)
+    rows [xc, yc, r], or (B, no, 3) with the circles of each trajectory; the descriptor carries trajectory 0's."""
 
     label = "circles"
 
     def __init__(self, n, m, circles, label="circles"):
-        self.circles = np.asarray(circles, dtype=np.float64).reshape(-1, 3)
+        self.n, self.m = n, m
+        self.circles = _obstacle_array(circles, 3, "CircleConstraints")
         self.label = label
 
+    @property
+    def batched(self):
+        return self.circles.ndim == 3
+
+    def for_traj(self, b):
+        """trajectory b's plain circle constraint"""
+        return CircleConstraints(self.n, self.m, self.circles[b], self.label) if self.batched else self
+
+    def slice(self, lo, hi):
+        return CircleConstraints(self.n, self.m, self.circles[lo:hi], self.label) if self.batched else self
+
+    def obstacle_rows(self, B):
+        """(B, no, 4) rows [xc, yc, 0, r]: the ABI's per-trajectory layout"""
+        c = self.circles if self.batched else np.broadcast_to(self.circles, (B,) + self.circles.shape)
+        out = np.zeros(c.shape[:2] + (4,))
+        out[..., 0:2] = c[..., 0:2]
+        out[..., 3] = c[..., 2]
+        return out
+
     def length(self, kind="stage"):
-        return len(self.circles) if kind == "stage" else 0
+        return self.circles.shape[-2] if kind == "stage" else 0
 
     def evaluate(self, x, u=None):
         if u is None:
             return np.zeros(0)
-        return np.array([circle_constraint(x, c[0], c[1], c[2]) for c in self.circles])
+        circles = self.circles[0] if self.batched else self.circles
+        return np.array([circle_constraint(x, c[0], c[1], c[2]) for c in circles])
 
     def to_abi(self):
-        return (abi.CON_CIRCLES, len(self.circles), self.circles.ravel())
+        circles = np.ascontiguousarray(self.circles[0] if self.batched else self.circles)
+        return (abi.CON_CIRCLES, len(circles), circles.ravel())
 
 
 class SphereConstraints(_Constraint):
     """Rows ``sphere_constraint(x, xc, yc, zc, r)`` (test/quadrotor_tests.jl:68-74,
-    problems/quad_obs.jl:64-69). Stage only."""
+    problems/quad_obs.jl:64-69). Stage only. ``spheres`` is (no, 4) rows [xc, yc, zc, r], or (B, no, 4) with the
+    spheres of each trajectory; the descriptor carries trajectory 0's."""
 
     label = "spheres"
 
     def __init__(self, n, m, spheres, label="spheres"):
-        self.spheres = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
+        self.n, self.m = n, m
+        self.spheres = _obstacle_array(spheres, 4, "SphereConstraints")
         self.label = label
 
+    @property
+    def batched(self):
+        return self.spheres.ndim == 3
+
+    def for_traj(self, b):
+        """trajectory b's plain sphere constraint"""
+        return SphereConstraints(self.n, self.m, self.spheres[b], self.label) if self.batched else self
+
+    def slice(self, lo, hi):
+        return SphereConstraints(self.n, self.m, self.spheres[lo:hi], self.label) if self.batched else self
+
+    def obstacle_rows(self, B):
+        """(B, no, 4) rows [xc, yc, zc, r]: the ABI's per-trajectory layout"""
+        return np.array(self.spheres if self.batched else np.broadcast_to(self.spheres, (B,) + self.spheres.shape))
+
     def length(self, kind="stage"):
-        return len(self.spheres) if kind == "stage" else 0
+        return self.spheres.shape[-2] if kind == "stage" else 0
 
     def evaluate(self, x, u=None):
         if u is None:
             return np.zeros(0)
-        return np.array([sphere_constraint(x, s[0], s[1], s[2], s[3]) for s in self.spheres])
+        spheres = self.spheres[0] if self.batched else self.spheres
+        return np.array([sphere_constraint(x, s[0], s[1], s[2], s[3]) for s in spheres])
 
     def to_abi(self):
-        return (abi.CON_SPHERES, len(self.spheres), self.spheres.ravel())
+        spheres = np.ascontiguousarray(self.spheres[0] if self.batched else self.spheres)
+        return (abi.CON_SPHERES, len(spheres), spheres.ravel())
 
 
 class ConstraintSet(list):
@@ -879,6 +931,9 @@ def _copy_constraints(cons):
     out.C = [ConstraintSet(c) for c in cons.C]
     return out
 
+
+# the constraints that can hold data per trajectory (batched, for_traj)
+_PER_TRAJECTORY = (GoalConstraint, CircleConstraints, SphereConstraints)
 
 # ----------------------------------------------------------------------------- problem
 
@@ -965,8 +1020,39 @@ class Problem:
                 return c.xf
         return None
 
+    def _abi_sets(self):
+        """The distinct constraint sets in the descriptor's order (build_desc): first appearance over the knots;
+        the terminal knot's set is its own even when it holds the stage knots' objects."""
+        sets, knot_set, keys = [], [], {}
+        for k in range(self.N):
+            cs = self.constraints[k]
+            if len(cs) == 0:
+                knot_set.append(-1)
+                continue
+            key = tuple(id(c) for c in cs) + (k == self.N - 1,)
+            if key not in keys:
+                keys[key] = len(sets)
+                sets.append(cs)
+            knot_set.append(keys[key])
+        return sets, knot_set
+
+    def trajectory_obstacles(self):
+        """(B, no, 4) rows [x0, y0, z0, r] (z0 = 0 for a circle) of every circle and sphere in the ABI's ordinal
+        order (tog_set_trajectory_obstacles: sets in the descriptor's order, constraints in their set's order,
+        then the constraint's own order; an object in two distinct sets is emitted once per set), or None when
+        no circle or sphere constraint holds per-trajectory data."""
+        obs = [c for cs in self._abi_sets()[0] for c in cs if isinstance(c, (CircleConstraints, SphereConstraints))]
+        if not any(c.batched for c in obs):
+            return None
+        return np.ascontiguousarray(np.concatenate([c.obstacle_rows(self.B) for c in obs], axis=1))
+
+    def has_trajectory_obstacles(self) -> bool:
+        return any(isinstance(c, (CircleConstraints, SphereConstraints)) and c.batched
+                   for cs in self.constraints.C for c in cs)
+
     def has_trajectory_data(self) -> bool:
-        return isinstance(self.obj, BatchObjective) or self.trajectory_goals() is not None
+        return (isinstance(self.obj, BatchObjective) or self.trajectory_goals() is not None
+                or self.has_trajectory_obstacles())
 
     def check_trajectory_data(self):
         """shapes of the per-trajectory data against the batch (ValueError)"""
@@ -980,6 +1066,11 @@ class Problem:
                 if isinstance(c, GoalConstraint) and c.batched:  # (rows at the terminal knot only)
                     if c.xf.shape[0] != B:
                         raise ValueError(f"goal_constraint holds {c.xf.shape[0]} goals, the problem {B} trajectories")
+                if isinstance(c, (CircleConstraints, SphereConstraints)) and c.batched:
+                    have = (c.circles if isinstance(c, CircleConstraints) else c.spheres).shape[0]
+                    if have != B:
+                        raise ValueError(f"{type(c).__name__} holds the obstacles of {have} trajectories, the "
+                                         f"problem {B} trajectories")
 
     def trajectory(self, b: int) -> "Problem":
         """The plain B = 1 problem of trajectory b: its objective, goal, x0, U, X."""
@@ -988,10 +1079,10 @@ class Problem:
         p = _copy.copy(self)
         p.obj = self.obj[b] if isinstance(self.obj, BatchObjective) else self.obj
         p.constraints = _copy_constraints(self.constraints)
-        memo = {}  # (one plain goal constraint per batched one: knots that share a set keep sharing it)
+        memo = {}  # (one plain constraint per batched one: knots that share a set keep sharing it)
         for k in range(self.N):
             p.constraints.C[k] = ConstraintSet(
-                memo.setdefault(id(c), c.for_traj(b)) if isinstance(c, GoalConstraint) else c
+                memo.setdefault(id(c), c.for_traj(b)) if isinstance(c, _PER_TRAJECTORY) else c
                 for c in self.constraints[k])
         p.batched = False
         p.x0 = self.x0[b:b + 1].copy()
@@ -1002,7 +1093,7 @@ class Problem:
 
     def batch_slice(self, lo: int, hi: int) -> "Problem":
         """Trajectories [lo, hi) as a batch of their own: their x0, U, X, and their members of a BatchObjective
-        and of per-trajectory goals (what a streamed solve's handle is created with, solve_stream)."""
+        and of per-trajectory goals and obstacles (what a streamed solve's handle is created with, solve_stream)."""
         if not 0 <= lo < hi <= self.B:
             raise IndexError(f"trajectories [{lo}, {hi}) of {self.B}")
         p = _copy.copy(self)
@@ -1012,7 +1103,8 @@ class Problem:
         memo = {}
         for k in range(self.N):
             p.constraints.C[k] = ConstraintSet(
-                memo.setdefault(id(c), GoalConstraint(c.xf[lo:hi])) if isinstance(c, GoalConstraint) and c.batched
+                memo.setdefault(id(c), GoalConstraint(c.xf[lo:hi]) if isinstance(c, GoalConstraint)
+                                else c.slice(lo, hi)) if isinstance(c, _PER_TRAJECTORY) and c.batched
                 else c for c in self.constraints[k])
         p.batched = True
         p.x0 = self.x0[lo:hi].copy()
@@ -1027,18 +1119,9 @@ class Problem:
         problem handed to tog_solve_altro, which builds minimum_time_problem itself)."""
         n, m, N = self.model.n, self.model.m, self.N
         stage, term = self.obj.stage, self.obj.terminal
-        sets, knot_set, keys = [], [], {}
-        for k in range(N):
-            cs = self.constraints[k]
-            if len(cs) == 0:
-                knot_set.append(-1)
-                continue
-            key = tuple(id(c) for c in cs) + (k == N - 1,)
-            if key not in keys:
-                keys[key] = len(sets)
-                sets.append([c.to_abi(m) if isinstance(c, (BoundConstraint, InfeasibleConstraint)) else c.to_abi()
-                             for c in cs])
-            knot_set.append(keys[key])
+        csets, knot_set = self._abi_sets()
+        sets = [[c.to_abi(m) if isinstance(c, (BoundConstraint, InfeasibleConstraint)) else c.to_abi() for c in cs]
+                for cs in csets]
         R = stage.R if stage.R.size else np.zeros((m, m))
         flags = (abi.PROB_INFEASIBLE if self.model.slack else 0) | (abi.PROB_MIN_TIME if self.model.min_time else 0)
         if tf_min and not self.model.min_time:
@@ -1117,8 +1200,8 @@ def max_violation(prob: Problem) -> float:
                 term = k == N - 1
                 vals_e, vals = [], []
                 for c in cs:
-                    if isinstance(c, GoalConstraint):
-                        c = c.for_traj(b)  # (a goal per trajectory)
+                    if isinstance(c, _PER_TRAJECTORY):
+                        c = c.for_traj(b)  # (a goal, or obstacles, per trajectory)
                     v = c.evaluate(X[k]) if term else c.evaluate(X[k], U[k])
                     if len(v) == 0:
                         continue

@@ -373,6 +373,37 @@ def config_quad_maze(B=8192, offset=0, N=201):
     return prob, AugmentedLagrangianSolverOptions()
 
 
+def config_quad_maze_obstacles(B=8192, offset=0, N=201):
+    """Config 4 with the obstacles of each trajectory its own (tog_set_trajectory_obstacles): every cylinder and
+    sphere centre moved by U(-1, 1) m per coordinate and its radius scaled by U(0.9, 1.1) (seed 4000+b; per
+    trajectory the cylinders' centre offsets (4, 2), their radius factors (4,), then the spheres' (3, 3) and
+    (3,)). x0, U0 and the options are config 4's."""
+    prob, opts = config_quad_maze(B=B, offset=offset, N=N)
+    cyl0 = next(c for c in prob.constraints[1] if isinstance(c, CircleConstraints))
+    sph0 = next(c for c in prob.constraints[1] if isinstance(c, SphereConstraints))
+    nc, ns = len(cyl0.circles), len(sph0.spheres)
+
+    def gen(r):
+        return np.concatenate([r.uniform(-1.0, 1.0, (nc, 2)).ravel(), r.uniform(0.9, 1.1, nc),
+                               r.uniform(-1.0, 1.0, (ns, 3)).ravel(), r.uniform(0.9, 1.1, ns)])
+
+    Z = _per_traj_rng(4000 + offset, B, gen)
+    cyl = np.tile(cyl0.circles, (B, 1, 1))
+    cyl[:, :, 0:2] += Z[:, :2 * nc].reshape(B, nc, 2)
+    cyl[:, :, 2] *= Z[:, 2 * nc:3 * nc]
+    o = 3 * nc
+    sph = np.tile(sph0.spheres, (B, 1, 1))
+    sph[:, :, 0:3] += Z[:, o:o + 3 * ns].reshape(B, ns, 3)
+    sph[:, :, 3] *= Z[:, o + 3 * ns:]
+    swap = {id(cyl0): CircleConstraints(13, 4, cyl, cyl0.label), id(sph0): SphereConstraints(13, 4, sph, sph0.label)}
+    cons = Constraints(N)
+    for k in range(N):
+        cons[k] = ConstraintSet(swap.get(id(c), c) for c in prob.constraints[k])
+    out = Problem(prob.model, prob.obj, constraints=cons, x0=prob.x0, xf=prob.xf, N=N, dt=prob.dt)
+    out._U[...] = prob._U
+    return out, opts
+
+
 def config_kuka(B=4096, offset=0):
     """Config 5: Kuka iiwa (n=14, m=7, N=51), AL-iLQR with the terminal goal and the notebook's options;
     x0[1:7] ~ U(-0.2, 0.2) (seed 4000+b), U0 = the hold trajectory at x0 (the notebook's own
