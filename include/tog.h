@@ -634,7 +634,9 @@ int32_t tog_solve_altro_ex(const tog_problem_desc* desc, const tog_altro_options
                            const double* x0, double* X, double* U, double* h, tog_altro_result* res);
 
 /* per-kernel timing with HIP events recorded on the handle's stream around every launch issued by
-   tog_solve_step (used by bench.py for the live roofline). */
+   tog_solve_step (used by bench.py for the live roofline). A convergence-tail step that issues its Jacobians
+   and its cost expansion as one launch (k_tail_prepare) times that launch under TOG_KERNEL_JACOBIAN and
+   records no TOG_KERNEL_EXPANSION launch. */
 enum tog_kernel_id {
   TOG_KERNEL_JACOBIAN = 0,
   TOG_KERNEL_BACKWARD = 1,

@@ -50,8 +50,9 @@ def main(path, last=4000):
               f"{1e3 * g[2]:10.2f}")
 
 
-def by_width(path, kernel="k_bwd", marker="k_jacobian", top_n=7):
-    """Batch steps (delimited by `marker` dispatches) binned by the launch width of the backward kernel
+def by_width(path, kernel="k_bwd", marker=("k_jacobian", "k_tail_prepare"), top_n=7):
+    """Batch steps (delimited by `marker` dispatches: a step's first launch is k_jacobian, or k_tail_prepare where
+    the tail fuses it with the expansion) binned by the launch width of the backward kernel
     (its workgroup count = ceil(n_active) of the last readback in a compacted tail launch): steps, mean
     step time and the mean time of each kernel per step in that bin. The team backward packs four
     trajectories into a workgroup, so where the tail may take it (--width-kernel) bin by a kernel that
@@ -61,7 +62,7 @@ def by_width(path, kernel="k_bwd", marker="k_jacobian", top_n=7):
     steps, cur = [], None
     for nm, s, e, gx, wx in rows:
         k = short(nm)
-        if k.startswith("void tog::" + marker) or k.startswith(marker):
+        if any(k.startswith("void tog::" + mk) or k.startswith(mk) for mk in marker):
             if cur:
                 steps.append(cur)
             cur = {"t0": s, "t1": e, "w": None, "k": collections.defaultdict(float)}

@@ -133,7 +133,8 @@ __device__ __forceinline__ void team_rows(const DevProblem* P, const DevBuffers&
   const double* lam = Bf.lam + ((size_t)b * N + k) * pmax;
   const double* mu = Bf.mu + ((size_t)b * N + k) * pmax;
   const unsigned long long tmask = (TEAM >= 64 ? ~0ull : ((1ull << TEAM) - 1ull)) << (team * TEAM);
-  const unsigned long long below = tmask & ((1ull << threadIdx.x) - 1ull);
+  // (team: the team's index within its wave, so team * TEAM + tl is the lane, also in a workgroup of several waves)
+  const unsigned long long below = tmask & ((1ull << (team * TEAM + tl)) - 1ull);
   int cx = 0, cu = 0;
   for (int base = 0; base < p; base += TEAM) {
     const int r = base + tl;
@@ -688,24 +689,32 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
 // mode 0: every knot; 1: only the dense ones (the others are on k_expand_u); 2: only the terminal knot
 // (one team per trajectory: no stage knot is dense). ALI: bit 0 the AL expansion, bit 1 the per-trajectory
 // variant (PT: q, r, qf and the goal rows' targets from trajectory b's tables)
+// Team idx of the launch (the body of k_expand_team and of k_tail_prepare's TEAM-lane blocks): (slot, knot) =
+// (idx / N, idx % N), in mode 2 slot idx's terminal knot. lteam: the team's index within its workgroup (its LDS
+// image), wteam: within its wave (the ballots of team_rows).
 template <class M, int SQRTI, int ALI>
-__global__ void __launch_bounds__(64) k_expand_team(const DevProblem* P, DevBuffers Bf, int mode) {
-  using Cfg = TeamCfg<M>;
-  extern __shared__ double expand_lds[];
-  const int team = threadIdx.x / Cfg::TEAM, tl = threadIdx.x % Cfg::TEAM;
+__device__ __forceinline__ void expand_team_item(const DevProblem* P, const DevBuffers& Bf, int mode, long long idx,
+                                                 double* lds, int lteam, int wteam, int tl) {
   const int N = P->N;
-  const long long idx = (long long)blockIdx.x * Cfg::TPW + team;
   const long long slot = (mode == 2) ? idx : idx / N;
   const int k = (mode == 2) ? N - 1 : (int)(idx - slot * N);
   const long long b = traj_of_slot(Bf, slot, P->B);
   if (b < 0) return;  // whole teams return together (DPP broadcasts stay within a team)
   if (!Bf.st[b].active || Bf.st[b].ls_pend) return;
   if (mode == 1 && k < N - 1 && !((ALI & 1) && P->knot_nx[k] > 0)) return;
-  double* tlds = expand_lds + (size_t)team * expand_team_stride<M>(P->pmax);
+  double* tlds = lds + (size_t)lteam * expand_team_stride<M>(P->pmax);
   if (k == N - 1)
-    team_expand<M, SQRTI != 0, (ALI & 1) != 0, true, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, team);
+    team_expand<M, SQRTI != 0, (ALI & 1) != 0, true, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, wteam);
   else
-    team_expand<M, SQRTI != 0, (ALI & 1) != 0, false, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, team);
+    team_expand<M, SQRTI != 0, (ALI & 1) != 0, false, (ALI & 2) != 0>(P, Bf, b, k, tlds, tl, wteam);
+}
+
+template <class M, int SQRTI, int ALI>
+__global__ void __launch_bounds__(64) k_expand_team(const DevProblem* P, DevBuffers Bf, int mode) {
+  using Cfg = TeamCfg<M>;
+  extern __shared__ double expand_lds[];
+  const int team = threadIdx.x / Cfg::TEAM, tl = threadIdx.x % Cfg::TEAM;
+  expand_team_item<M, SQRTI, ALI>(P, Bf, mode, (long long)blockIdx.x * Cfg::TPW + team, expand_lds, team, team, tl);
 }
 
 // k_expand_u: the square-root expansion of the knots whose Q.xx is the problem constant (stage knots
@@ -864,11 +873,11 @@ __device__ __forceinline__ void quad_expand(const DevProblem* P, const DevBuffer
   }
 }
 
+// 4-lane team idx of the launch (the body of k_expand_u and of k_tail_prepare's 4-lane blocks): (slot, knot) =
+// (idx / (N - 1), idx % (N - 1))
 template <class M, int ALI>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_expand_u(const DevProblem* P, DevBuffers Bf) {
-  const int team = threadIdx.x / 4, tl = threadIdx.x % 4;
+__device__ __forceinline__ void expand_quad_item(const DevProblem* P, const DevBuffers& Bf, long long idx, int tl) {
   const int N = P->N;
-  const long long idx = (long long)blockIdx.x * 16 + team;
   const long long slot = idx / (N - 1);
   const int k = (int)(idx - slot * (N - 1));
   const long long b = traj_of_slot(Bf, slot, P->B);
@@ -876,6 +885,40 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
   if (!Bf.st[b].active || Bf.st[b].ls_pend) return;
   if ((ALI & 1) && P->knot_nx[k] > 0) return;  // a dense knot: k_expand_team
   quad_expand<M, (ALI & 1) != 0, (ALI & 2) != 0>(P, Bf, b, k, tl);
+}
+
+template <class M, int ALI>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_expand_u(const DevProblem* P, DevBuffers Bf) {
+  const int team = threadIdx.x / 4, tl = threadIdx.x % 4;
+  expand_quad_item<M, ALI>(P, Bf, (long long)blockIdx.x * 16 + team, tl);
+}
+
+// k_tail_prepare: a tail step's Jacobians and cost expansion in one launch (tog_plan::tail_prepare has the grid:
+// blocks [0, jac) run k_jacobian's body, [jac, jac + quad) k_expand_u's, the rest k_expand_team's, each on the
+// work item the separate kernel would give it, so every value is formed by the same operations). The three read X,
+// U, λ and μ and write AB and E: none reads another's output. No role uses a workgroup barrier (the teams order
+// their LDS traffic within their wave), so a thread without work returns. One wave per SIMD, as k_jacobian: the
+// launch is a few blocks beside idle CUs, and its registers are the largest role's.
+template <class M, int INTEG, int SQRTI, int ALI, int W>
+__global__ void __launch_bounds__(tog_plan::PREP_THREADS) __attribute__((amdgpu_waves_per_eu(TOG_JAC_WAVES)))
+k_tail_prepare(const DevProblem* __restrict__ P, DevBuffers Bf, long long jtotal, unsigned jac, unsigned quad,
+               int mode) {
+  using Cfg = TeamCfg<M>;
+  extern __shared__ double expand_lds[];
+  const int role = tog_plan::prepare_role(blockIdx.x, jac, quad);
+  const long long blk = (long long)tog_plan::prepare_block(blockIdx.x, jac, quad);
+  if (role == tog_plan::PREP_JAC) {
+    const long long t = blk * tog_plan::PREP_THREADS + threadIdx.x;
+    if (t >= jtotal) return;
+    jacobian_item<M, INTEG, W>(P, Bf, t);
+  } else if (role == tog_plan::PREP_QUAD) {
+    if constexpr (M::m <= 4 && Cfg::TEAM == 16)
+      expand_quad_item<M, ALI>(P, Bf, blk * tog_plan::PREP_QUADS + threadIdx.x / 4, threadIdx.x % 4);
+  } else {
+    const int lteam = threadIdx.x / Cfg::TEAM, tl = threadIdx.x % Cfg::TEAM;
+    expand_team_item<M, SQRTI, ALI>(P, Bf, mode, blk * (tog_plan::PREP_THREADS / Cfg::TEAM) + lteam, expand_lds, lteam,
+                                    lteam % Cfg::TPW, tl);
+  }
 }
 
 #ifndef TOG_BWD_WAVES

@@ -1,8 +1,9 @@
 // Host arithmetic that decides which kernel code a handle runs (tog_create): the run-time flag -> template
 // constant dispatcher of the launch table (tog_launch.hpp), the stage-cost table with its Cholesky factors and
-// diagonal-cost class, the Q.xx pattern of the packed expansion records, and the line search's rollout-kernel choice
-// with the LDS layout arithmetic of the tail rollouts. Plain C++ with no device runtime in it, so that a stand-alone
-// program can run it under the host sanitizers (tests/c/host_plan_host.cpp, rollout_plan_host.cpp). tog_kernels.hpp
+// diagonal-cost class, the Q.xx pattern of the packed expansion records, the grid of a tail step's fused preparation
+// launch, and the line search's rollout-kernel choice with the LDS layout arithmetic of the tail rollouts. Plain C++
+// with no device runtime in it, so that a stand-alone program can run it under the host sanitizers
+// (tests/c/host_plan_host.cpp, rollout_plan_host.cpp, prepare_plan_host.cpp). tog_kernels.hpp
 // includes it too: the spec_tail* constants and constexpr size functions below are the kernels' own LDS layout
 // (used in device code), so the plan and the kernels cannot disagree about it.
 #pragma once
@@ -32,6 +33,58 @@ enum TailBackward { TAIL_BWD_TEAM = 0, TAIL_BWD_QUAD = 1 };
 constexpr long long TAIL_QUAD_ROUNDS = 1;
 inline TailBackward tail_backward(long long width, int cus) {
   return (cus > 0 && width <= TAIL_QUAD_ROUNDS * (long long)cus) ? TAIL_BWD_QUAD : TAIL_BWD_TEAM;
+}
+
+// The preparation of a tail step: the Jacobians (k_jacobian) and the cost expansion (k_expand_u on 4-lane teams,
+// k_expand_team on TEAM-lane teams) read X, U, λ and μ only and none reads another's output, so in the convergence
+// tail, where each is a handful of waves waiting on its own loads, they go out as one launch, k_tail_prepare. Its
+// grid is three contiguous ranges of PREP_THREADS-thread blocks, [Jacobian | 4-lane teams | TEAM-lane teams]; a
+// block takes its role from its index (prepare_role: uniform over the block, so every wave runs one role and the
+// team code's DPP broadcasts stay within whole teams) and runs the separate kernel's body on the separate kernel's
+// work item: thread t of the Jacobian range is (slot, knot, chunk) t; 4-lane team i of the second range is (slot,
+// knot) i over the N - 1 stage knots; TEAM-lane team i of the third is (slot, knot) i over all N knots, or slot i's
+// terminal knot in mode 2.
+constexpr int PREP_THREADS = 256;
+constexpr int PREP_QUADS = PREP_THREADS / 4;  // 4-lane teams of a block
+enum PrepareRole { PREP_JAC = 0, PREP_QUAD = 1, PREP_TEAM = 2 };
+// the role of block `blk` of a grid whose first `jac` blocks are the Jacobian's and next `quad` the 4-lane teams',
+// and the block's index within its role's range
+constexpr int prepare_role(unsigned blk, unsigned jac, unsigned quad) {
+  return blk < jac ? PREP_JAC : (blk - jac < quad ? PREP_QUAD : PREP_TEAM);
+}
+constexpr unsigned prepare_block(unsigned blk, unsigned jac, unsigned quad) {
+  return blk < jac ? blk : (blk - jac < quad ? blk - jac : blk - jac - quad);
+}
+struct TailPrepare {
+  bool fused = false;                    // one k_tail_prepare launch (else the separate kernels, as in the bulk)
+  unsigned jac = 0, quad = 0, team = 0;  // blocks of each range
+  unsigned lds = 0;                      // dynamic LDS bytes: the TEAM-lane teams' images
+  unsigned blocks() const { return jac + quad + team; }
+};
+// tail, bwd_team: DevBuffers::tail and the handle's team backward path; plain_jac: the model's Jacobians are one
+// k_jacobian launch (not the minimum-time kernel, not the Kuka's stage chain); split: TOG_TAIL_PREPARE=split.
+// width: slots of the launch; nch: Jacobian chunks per knot; team_lanes: lanes of a wide team; mode: 0 every knot on
+// the wide teams (no 4-lane range), 1 the 4-lane teams and the dense knots among all N on the wide ones, 2 the
+// 4-lane teams and the terminal knot alone on the wide ones (k_expand_team's mode); team_stride: doubles of one
+// wide team's LDS image (expand_team_stride). A launch whose image is above SPEC_LDS_MAX, or whose grid does not
+// fit 31 bits, stays split.
+inline TailPrepare tail_prepare(int tail, int bwd_team, bool plain_jac, bool split, long long width, int N, int nch,
+                                int team_lanes, int mode, int team_stride) {
+  TailPrepare p;
+  if (!tail || !bwd_team || !plain_jac || split || width <= 0 || N < 2) return p;
+  const long long tpb = PREP_THREADS / team_lanes;
+  const long long jt = width * (long long)(N - 1) * nch, qt = mode ? width * (long long)(N - 1) : 0;
+  const long long tt = mode == 2 ? width : width * (long long)N;
+  const long long jb = (jt + PREP_THREADS - 1) / PREP_THREADS, qb = (qt + PREP_QUADS - 1) / PREP_QUADS;
+  const long long tb = (tt + tpb - 1) / tpb;
+  const long long lds = (long long)sizeof(double) * tpb * team_stride;
+  if (lds > 64 * 1024 || jb + qb + tb > 0x7fffffffLL) return p;
+  p.fused = true;
+  p.jac = (unsigned)jb;
+  p.quad = (unsigned)qb;
+  p.team = (unsigned)tb;
+  p.lds = (unsigned)lds;
+  return p;
 }
 
 // The speculative rollout kernels of the line search (tog_kernels.hpp) and which of them a launch takes.

@@ -4,7 +4,8 @@
 //   k_init          solve!/reset! + initial rollout + initial (AL) cost      ilqr_methods.jl:3-20, augmented_lagrangian_methods.jl:2-16
 //   k_rollout_open  rollout!(prob)                                           src/rollout.jl:25-38
 //   k_jacobian      jacobian!(prob, solver): ForwardDiff duals through RK3/4 src/model.jl:301-306, 491-522
-//   k_backward      cost_expansion! + backwardpass! (std / sqrt)             ilqr_methods.jl:55-62, backward_pass.jl:1-192
+//   k_tail_prepare  k_jacobian + the team cost expansion as one launch (convergence tail; tog_bwd_team.hpp)
+//   k_backward      cost_expansion! + backwardpass! (std / sqrt)           ilqr_methods.jl:55-62, backward_pass.jl:1-192
 //   k_forward       forwardpass! line search + solve! bookkeeping + AL dual/penalty update
 //                                                                           forward_pass.jl:5-85, ilqr_methods.jl:21-45,
 //                                                                           augmented_lagrangian_methods.jl:53-126
@@ -596,18 +597,17 @@ __global__ void __launch_bounds__(64) k_rollout(const DevProblem* __restrict__ P
 // src/model.jl:491-512 (ForwardDiff.jacobian! of fd_aug!); the dt column is never consumed by
 // iLQR (backward_pass.jl:30,110) and is not materialised.
 // =============================================================================================
-template <class M, int INTEG, int W>
 #ifndef TOG_JAC_WAVES
 #define TOG_JAC_WAVES 1
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TOG_JAC_WAVES)))
-k_jacobian(const DevProblem* __restrict__ P, DevBuffers Bf, long long total) {
+// work item t < total of the launch: (slot, knot, chunk) = (t / NCH / (N - 1), t / NCH % (N - 1), t % NCH); the body
+// of k_jacobian and of k_tail_prepare's Jacobian blocks
+template <class M, int INTEG, int W>
+__device__ __forceinline__ void jacobian_item(const DevProblem* P, const DevBuffers& Bf, long long t) {
   // an infeasible model (ModelTraits<M>::slack) differentiates its base model only; its slack
   // columns are the identity (src/model.jl:771-774)
   using Mb = typename ModelTraits<M>::Base;
   constexpr int n = M::n, m = M::m, L = n + m, mb = Mb::m, Lb = n + mb, NCH = (Lb + W - 1) / W;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
   const int N = P->N;
   const int c = (int)(t % NCH);
   const long long bk = t / NCH;
@@ -644,6 +644,14 @@ k_jacobian(const DevProblem* __restrict__ P, DevBuffers Bf, long long total) {
 #pragma unroll
       for (int i = 0; i < n; i++) out[i + n * (Lb + j)] = (i == j) ? 1.0 : 0.0;
   }
+}
+
+template <class M, int INTEG, int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TOG_JAC_WAVES)))
+k_jacobian(const DevProblem* __restrict__ P, DevBuffers Bf, long long total) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  jacobian_item<M, INTEG, W>(P, Bf, t);
 }
 
 // Minimum-time model (add_min_time_controls, src/solvers/altro/minimum_time.jl:91-96): the base

@@ -47,6 +47,10 @@ struct ModelOps {
                    hipStream_t);
   // k_expand_team: the cost expansion records the team backward kernel reads (tog_bwd_team.hpp)
   void (*expand)(const DevProblem*, const DevBuffers&, long long B, int N, int pmax, int sqrt, int al, hipStream_t);
+  // k_tail_prepare: jacobian and expand as one launch in the convergence tail (1), or nothing launched (0: the caller
+  // launches the two); team: the handle's team backward path
+  int (*tail_prepare)(const DevProblem*, const DevBuffers&, long long B, int N, int pmax, int integ, int sqrt, int al,
+                      int team, hipStream_t);
   void (*forward)(const DevProblem*, const DevBuffers&, long long B, int integ, int mode, int bookkeeping,
                   const double* Jprev, double* Jout, hipStream_t, const StreamPair* sp);
   void (*cost)(const DevProblem*, const DevBuffers&, long long B, int al, int use_bar, double* J, hipStream_t);
@@ -203,25 +207,31 @@ struct ModelLaunch {
       });
     });
   }
+  // Which knots k_expand_team takes (its mode argument). Square root, at most 4 controls, 16-lane teams: the knots
+  // with a constant Q.xx on 4-lane teams (k_expand_u), the dense ones on k_expand_team (mode 1; only the terminal
+  // knot when no stage knot has a state row, mode 2); otherwise, and with TOG_EXPAND_QUAD=0 (A/B checks), every
+  // knot on k_expand_team (mode 0).
+  static int expand_mode(const DevBuffers& Bf, int sq, int al) {
+    if constexpr (M::m <= 4 && TeamCfg<M>::TEAM == 16) {
+      const char* eq = getenv("TOG_EXPAND_QUAD");
+      if (sq && !(eq && eq[0] == '0')) return (al && Bf.dense_stage_knots) ? 1 : 2;
+    }
+    return 0;
+  }
   static void expand(const DevProblem* P, const DevBuffers& Bf, long long B, int N, int pmax, int sq, int al,
                      hipStream_t st) {
     if constexpr (M::m <= M::n && M::n + 1 <= 16 && !ModelTraits<M>::min_time) {
       constexpr int TPW = TeamCfg<M>::TPW;
       const unsigned sm = (unsigned)(sizeof(double) * TPW * expand_team_stride<M>(pmax));
-      // square root, at most 4 controls, 16-lane teams: the knots with a constant Q.xx on 4-lane teams
-      // (k_expand_u), the dense ones on k_expand_team (only the terminal knot when no stage knot has a
-      // state row); TOG_EXPAND_QUAD=0 keeps every knot on k_expand_team, for A/B checks
-      int mode = 0;
+      const int mode = expand_mode(Bf, sq, al);
       const int ali = ali_expand(al, Bf.tv);
       if constexpr (M::m <= 4 && TeamCfg<M>::TEAM == 16) {
-        const char* eq = getenv("TOG_EXPAND_QUAD");
-        if (sq && !(eq && eq[0] == '0')) {
+        if (mode) {
           const long long qteams = B * (long long)(N - 1);
           pick<0, 1, 2, 3>(ali, [&](auto ali_c) {
             hipLaunchKernelGGL((k_expand_u<M, decltype(ali_c)::value>), dim3((unsigned)((qteams + 15) / 16)), dim3(64),
                                0, st, P, Bf);
           });
-          mode = (al && Bf.dense_stage_knots) ? 1 : 2;
         }
       }
       const long long teams = (mode == 2) ? B : B * (long long)N;
@@ -233,6 +243,37 @@ struct ModelLaunch {
         });
       });
     }
+  }
+  // The Jacobians and the expansion of a tail step as one k_tail_prepare launch where tog_plan::tail_prepare says so;
+  // returns 1 when it launched, 0 when the step takes jacobian() and expand(). Instantiated for the models whose
+  // Jacobians are one k_jacobian launch under an explicit integrator (the Kuka's kernels, stage chain or not, live
+  // on scratch that the other two roles would inherit). TOG_TAIL_PREPARE=split keeps the separate launches, for A/B
+  // checks (read per launch: tests switch it within one process).
+  static int tail_prepare(const DevProblem* P, const DevBuffers& Bf, long long B, int N, int pmax, int integ, int sq,
+                          int al, int team, hipStream_t st) {
+    if constexpr (M::m <= M::n && M::n + 1 <= 16 && !ModelTraits<M>::min_time && Mb::id != TOG_MODEL_KUKA &&
+                  ModelTraits<M>::explicit_ok) {
+      constexpr int NCH = (Mb::n + Mb::m + JW - 1) / JW;
+      const bool plain = integ == TOG_RK3 || integ == TOG_RK4 || integ == TOG_MIDPOINT;
+      const char* tp = getenv("TOG_TAIL_PREPARE");
+      const int mode = expand_mode(Bf, sq, al);
+      const tog_plan::TailPrepare pl = tog_plan::tail_prepare(Bf.tail, team, plain, tp && !strcmp(tp, "split"), B, N, NCH,
+                                                              TeamCfg<M>::TEAM, mode, expand_team_stride<M>(pmax));
+      if (!pl.fused) return 0;
+      const long long jtotal = B * (long long)(N - 1) * NCH;
+      const int ali = ali_expand(al, Bf.tv);
+      pick<TOG_RK3, TOG_RK4, TOG_MIDPOINT>(integ, [&](auto ic) {
+        pick<0, 1>(sq ? 1 : 0, [&](auto sq_c) {
+          pick<0, 1, 2, 3>(ali, [&](auto ali_c) {
+            hipLaunchKernelGGL(
+                (k_tail_prepare<M, decltype(ic)::value, decltype(sq_c)::value, decltype(ali_c)::value, JW>),
+                dim3(pl.blocks()), dim3(tog_plan::PREP_THREADS), pl.lds, st, P, Bf, jtotal, pl.jac, pl.quad, mode);
+          });
+        });
+      });
+      return 1;
+    }
+    return 0;
   }
   template <int INTEG>
   static void spec(const DevProblem* P, const DevBuffers& Bf, long long B, int mode, int lo, int cnt, const int* list,
@@ -473,6 +514,7 @@ struct ModelLaunch {
     o.jacobian = jacobian;
     o.backward = backward;
     o.expand = expand;
+    o.tail_prepare = tail_prepare;
     o.forward = forward;
     o.cost = cost;
     o.rollout = rollout;

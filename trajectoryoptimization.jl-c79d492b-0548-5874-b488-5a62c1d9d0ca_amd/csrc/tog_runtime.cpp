@@ -1883,8 +1883,15 @@ int32_t tog_solve_step(tog_handle* h, int32_t nsteps) {
     Bt.act_count = h->d_act_count;
   }
   for (int i = 0; i < nsteps; i++) {
-    timed(h, TOG_KERNEL_JACOBIAN, [&] { h->ops->jacobian(h->dP, Bt, Bl, h->N, h->integ, h->stream); });
-    if (h->bwd_team)
+    // a tail step's Jacobians and expansion as one launch (k_tail_prepare, timed as the Jacobian: no expansion
+    // launch is recorded for such a step), or the two as in the bulk
+    int fused = 0;
+    timed(h, TOG_KERNEL_JACOBIAN, [&] {
+      fused = h->ops->tail_prepare(h->dP, Bt, Bl, h->N, h->pmax, h->integ, h->opts.square_root, al, h->bwd_team,
+                                   h->stream);
+      if (!fused) h->ops->jacobian(h->dP, Bt, Bl, h->N, h->integ, h->stream);
+    });
+    if (h->bwd_team && !fused)
       timed(h, TOG_KERNEL_EXPANSION, [&] {
         h->ops->expand(h->dP, Bt, Bl, h->N, h->pmax, h->opts.square_root, al, h->stream);
       });
