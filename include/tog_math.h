@@ -138,6 +138,29 @@ TOG_HD double tog_rsqrt(double y) {
   return (y > 0.0 && y < INFINITY) ? r : ((y == 0.0) ? INFINITY : ((y == INFINITY) ? 0.0 : NAN));
 }
 
+/* tog_rsqrt with the input's class applied as selects on the finished Newton value: the same seed, the same
+ * four steps and the same result bits for every y (tests/test_rsqrt_select.py), as straight-line code. The
+ * nested test above compiles to an exec-masked branch on the GPU, which a wave takes whenever one of its lanes
+ * holds a y outside (0, Inf); the downdate wave of k_bwd_quad always has such lanes (the ones past the m
+ * columns), so it calls this form. (The seed is formed in unsigned arithmetic: the same bits, and defined for
+ * the small negative y at which the signed difference above overflows.) */
+TOG_HD double tog_rsqrt_select(double y) {
+  long long i;
+  double r;
+  __builtin_memcpy(&i, &y, sizeof(i));
+  const unsigned long long s = 0x5FE6EB50C7B537A9ULL - (unsigned long long)(i >> 1);
+  __builtin_memcpy(&r, &s, sizeof(r));
+  const double h = 0.5 * y;
+  for (int k = 0; k < 4; k++) {
+    const double hr = h * r;
+    const double e = fma(-hr, r, 0.5);
+    r = fma(r, e, r);
+  }
+  r = (y == 0.0) ? INFINITY : r;
+  r = (y == INFINITY) ? 0.0 : r;
+  return (y >= 0.0) ? r : NAN;
+}
+
 /* c = sqrt(y) of chol_minus as y * tog_rsqrt(y), with the reference's c = sqrt(0) = 0 at y == 0
  * (s^2 == 1 exactly; y * rsqrt(y) would be 0 * Inf = NaN there). The reciprocal stays Inf. */
 TOG_HD double tog_rs_c(double y, double rc) { return (y == 0.0) ? 0.0 : y * rc; }

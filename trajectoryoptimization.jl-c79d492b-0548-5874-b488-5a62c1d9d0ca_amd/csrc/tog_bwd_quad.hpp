@@ -50,12 +50,27 @@ struct QuadLayout {  // doubles in the workgroup's LDS
   static constexpr int TOTAL = TAGS + (NTAGS + 1) / 2;
 };
 
+// The drain between the knot's two QRs (wave D's last steps and its epilogue in front of B2b), part by part, each a
+// compile-time switch so that it can be measured alone (-DTOG_QUAD_DRAIN=<bits>; DESIGN.md §5 has the measurements,
+// and the fourth part, wave A's reads behind B2b in one LDS round trip, which was measured slower and is not here).
+// No part changes a value a lane computes or the order of its operations.
+//   1  wave D's epilogue without exec branches: tmp2's rows stored by every lane (the lanes past the rows into
+//      `pad`), its strict lower triangle zeroed once before the knot loop, flg[2] stored by every lane, and the
+//      u[0] products formed in their steps instead of as one chain behind the last step
+//   2  the drain steps t >= n run only the entries and lanes still in play
+//   4  wave D's 1/sqrt by tog_rsqrt_select (no exec branch behind the Newton chain)
+#ifndef TOG_QUAD_DRAIN
+#define TOG_QUAD_DRAIN 7
+#endif
+
 template <class M, int ALI>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
   using Cfg = TeamCfg<M>;
   using D = QuadLayout<M>;
   constexpr bool SQRT = true, AL = (ALI & 1) != 0, TV = (ALI & 2) != 0;  // TV: a time-varying Objective
+  constexpr bool D_EPI = (TOG_QUAD_DRAIN & 1) != 0, D_STEPS = (TOG_QUAD_DRAIN & 2) != 0,
+                 D_RSEL = (TOG_QUAD_DRAIN & 4) != 0;
   constexpr int n = M::n, m = M::m, L = n + m, TEAM = Cfg::TEAM, NQ = nq_of<M>(), NE = ne_of<M>();
   static_assert(TEAM == 16 && m <= n && n + 1 <= 16, "quad kernel: 16-lane DPP rows");
   __shared__ double lds[D::TOTAL];
@@ -96,6 +111,15 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
   constexpr int SOFF = n * n;
   constexpr int TB = 32;
   double* bus2 = busA + TB + n * m;
+  if constexpr (D_EPI) {
+    // tmp2's strict lower triangle: zeros that only wave D ever writes (its rows' stores cover the upper triangle
+    // alone), so once per launch instead of once per knot; the barriers ahead of the first knot publish them
+    if (wv == 3 && tl < m) {
+#pragma unroll
+      for (int jj = 0; jj < m; jj++)
+        if (jj < tl) bus2[2 * m * m + tl + m * jj] = 0.0;
+    }
+  }
   const bool store_S = (flags & TOG_BP_STORE_S) && Bf.Sdbg;
   const bool state_reg = (P->o.bp_reg_type == 1);
   const double dt = P->dt;
@@ -590,27 +614,46 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
         }
         double ru = 1.0 / u[0];
         bool okd = true;
-        auto chol_step = [&](int t) {
+        // Step t: lane tl rotates input row t - tl into its factor row, entry kk of both being column tl + kk.
+        // A drain step t = n + dr has no new input row: the lanes tl > dr are still at work, on the m - tl <=
+        // m - 1 - dr entries of their rows, and lane 0's injected row is not consumed by anyone. D_STEPS runs
+        // just that (the dropped entries and lanes never reach a stored value: lane tl's entries kk >= m - tl
+        // only ever feed entries kk >= m - tl' of the lanes tl' > tl).
+        auto chol_step = [&](auto tc) {
+          constexpr int t = decltype(tc)::value;
+          constexpr int dr = t - n;
+          constexpr bool DRAIN = D_STEPS && dr >= 0;
+          constexpr int E = DRAIN ? m - 1 - dr : m;  // entries in play
           const int r = t - tl;
-          const bool act = colu && r >= 0 && r < n;
+          const bool act = DRAIN ? (colu && tl > dr) : (colu && r >= 0 && r < n);
           double x[m];
+          if constexpr (DRAIN) {
 #pragma unroll
-          for (int kk = 0; kk + 1 < m; kk++) x[kk] = row_shr1_or(w[kk + 1], x0[kk]);  // (lane 0: x0)
-          x[m - 1] = (tl == 0) ? x0[m - 1] : 0.0;
+            for (int kk = 0; kk < E; kk++) x[kk] = row_shr1(w[kk + 1]);
+          } else {
+#pragma unroll
+            for (int kk = 0; kk + 1 < m; kk++) x[kk] = row_shr1_or(w[kk + 1], x0[kk]);  // (lane 0: x0)
+            x[m - 1] = (tl == 0) ? x0[m - 1] : 0.0;
+          }
           const double sn = x[0] * ru;
           const double s2 = sn * sn;
           okd = okd && !(act && s2 > 1.0);
           const double y = 1.0 - s2;
-          const double rc = tog_rsqrt(y);
+          double rc;
+          if constexpr (D_RSEL) rc = tog_rsqrt_select(y);
+          else rc = tog_rsqrt(y);
           const double cs = tog_rs_c(y, rc);
           w[0] = x[0];
 #pragma unroll
-          for (int kk = 1; kk < m; kk++) {
+          for (int kk = 1; kk < E; kk++) {
             const double tmp = (u[kk] - sn * x[kk]) * rc;
             w[kk] = cs * x[kk] - sn * tmp;
             u[kk] = act ? tmp : u[kk];
           }
           u[0] = act ? cs * u[0] : u[0];
+          // (u[0] is read again only by the epilogue's store: left alone, the compiler sinks the n + m - 1
+          // products there, a serial chain behind the last step, on the knot's critical path)
+          if constexpr (D_EPI) u[0] = opaque(u[0]);
           ru = act ? ru * rc : ru;
         };
         static_for<0, n>([&](auto tc) {
@@ -626,22 +669,32 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
           tag_wait(&t1f[t]);
 #pragma unroll
           for (int kk = 0; kk < m; kk++) x0[kk] = busA[TB + t * m + kk];
-          chol_step(t);
+          chol_step(tc);
         });
         DPROF(18);
-        static_for<n, n + m - 1>([&](auto tc) { chol_step(decltype(tc)::value); });  // (lane 0 idle: input row n-1)
+        static_for<n, n + m - 1>([&](auto tc) { chol_step(tc); });  // (lane 0 idle: input row n-1)
+        DPROF(19);
         const unsigned long long rowmask = 0xFFFFull << (threadIdx.x & 48);
         const bool pd_fail = (__ballot(!okd) & rowmask) != 0ull;
-        if (colu) {
-#pragma unroll
-          for (int jj = 0; jj < m; jj++)
-            if (jj < tl) bus2[2 * m * m + tl + m * jj] = 0.0;
+        if constexpr (D_EPI) {
+          // every lane stores (as the QRs' `release` does): no exec change between the last step and B2b. The
+          // four DPP rows hold the same team, so every lane has the same verdict.
 #pragma unroll
           for (int kk = 0; kk < m; kk++)
-            if (tl + kk < m) bus2[2 * m * m + tl + m * (tl + kk)] = u[kk];
+            *((colu && tl + kk < m) ? bus2 + 2 * m * m + tl + m * (tl + kk) : pad + tl) = u[kk];
+          flg[2] = pd_fail ? 1 : 0;
+        } else {
+          if (colu) {
+#pragma unroll
+            for (int jj = 0; jj < m; jj++)
+              if (jj < tl) bus2[2 * m * m + tl + m * jj] = 0.0;
+#pragma unroll
+            for (int kk = 0; kk < m; kk++)
+              if (tl + kk < m) bus2[2 * m * m + tl + m * (tl + kk)] = u[kk];
+          }
+          if (threadIdx.x == 192) flg[2] = pd_fail ? 1 : 0;
         }
-        if (threadIdx.x == 192) flg[2] = pd_fail ? 1 : 0;
-        DPROF(19);
+        DPROF(28);
       }
       if (faithful) kmin = k < kmin ? k : kmin;
       __syncthreads();  // B2b: tmp2, the verdict and the downdate's failure flag on the bus
@@ -685,6 +738,7 @@ k_bwd_quad(const DevProblem* P, DevBuffers Bf, int flags) {
           for (int l = 0; l < m; l++) v = fma(U2p[i + m * l], Kc[l], v);
           a[n + i] = v;
         }
+        DPROF(29);
         // release row j of S_k after column step j: the row (zeros left of the diagonal), then its tag
         auto release = [&](auto jc, const double (&r)[RS]) {
           constexpr int j = decltype(jc)::value;

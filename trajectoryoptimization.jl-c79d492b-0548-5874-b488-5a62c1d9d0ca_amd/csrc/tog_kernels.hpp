@@ -1831,7 +1831,7 @@ attempt:
 // Section timers of the knot loop (build with -DTOG_BWD_PROF; read with tog_bwd_prof_read): shader
 // clock deltas (s_memtime) summed per wave into SGPR accumulators, flushed once per wave.
 #ifdef TOG_BWD_PROF
-constexpr int BPROF_N = 32;  // 0-19 the backward kernels, 20-27 the tail rollouts
+constexpr int BPROF_N = 32;  // 0-19 and 25-29 the backward kernels, 20-24 the tail rollouts
 static __device__ unsigned long long tog_bwd_prof[BPROF_N];
 // per-block LDS accumulators (non-returning ds_add_u64: no wait), only the last stamp in SGPRs
 #define BPROF_DECL                                             \
