@@ -38,7 +38,7 @@ extern "C" {
 /* still 5: the streamed solves (tog_finished, tog_get_slots, tog_refill, tog_refill_tables, tog_solve_stream,
       tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed;
       likewise tog_rollout_plan (a query for tests) and tog_set_trajectory_obstacles (per-trajectory circle and
-      sphere data) */
+      sphere data) and tog_set_trajectory_bounds (per-trajectory state and control limits) */
 #define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
@@ -167,11 +167,11 @@ typedef struct tog_constraint_set {
    (src/cost.jl:112-157, src/objective.jl:102-114) and per-knot constraint sets
    (src/constraint_sets.jl:157-206). One problem, B independent trajectories
    that differ in x0 and the initial controls U0 and, once set on the handle, in the
-   linear and constant terms of their cost, in their goal and in the centres and radii
-   of their circle and sphere obstacles (tog_set_trajectory_costs,
-   tog_set_trajectory_goals, tog_set_trajectory_obstacles). The cost Hessians, the
-   dynamics, the bounds, the user constraints and the number and kind of the obstacles
-   are the batch's. */
+   linear and constant terms of their cost, in their goal, in the centres and radii
+   of their circle and sphere obstacles and in the limits of their bound rows
+   (tog_set_trajectory_costs, tog_set_trajectory_goals, tog_set_trajectory_obstacles,
+   tog_set_trajectory_bounds). The cost Hessians, the dynamics, the user constraints,
+   the number and kind of the obstacles and which bounds have a row are the batch's. */
 typedef struct tog_problem_desc {
   int32_t model;      /* tog_model_id                       */
   int32_t integrator; /* tog_integrator                     */
@@ -403,6 +403,19 @@ int32_t tog_set_trajectory_goals(tog_handle* h, const double* xf);
    tog_solve_pn, tog_refill, tog_refill_tables, tog_solve_stream and tog_solve_stream_tables return
    TOG_ERR_UNSUPPORTED (they would read the descriptor's obstacles). */
 int32_t tog_set_trajectory_obstacles(tog_handle* h, const double* obs);
+/* Per-trajectory bounds: the limits of the TOG_CON_BOUND rows. bnd: (nb, B), host pointer; entry (j, b) is the
+   limit of the bound row with ordinal j for trajectory b. nb counts the bound rows kept over desc.sets[], and j
+   is the row's ordinal in that order: sets in order, constraints in their set's order, and within a bound
+   constraint the kept rows in the order [x_max; u_max; x_min; u_min]. Kept: the finite entries of a trimmed
+   constraint (count 0), every entry of an untrimmed one (count 1); no u rows when only the terminal knot uses
+   the set. A set used at many knots contributes once, a set that no knot uses still counts. NULL restores the
+   descriptor's values. Replacement, lifetime and the split on a tog_create_multi handle are as for
+   tog_set_trajectory_costs. TOG_ERR_ARG when the problem has no bound row, for a NaN anywhere and for a
+   non-finite value at a row of a trimmed constraint (the row exists because the bound is finite; the table in
+   place stays); TOG_ERR_UNSUPPORTED on a TOG_PROB_INFEASIBLE or TOG_PROB_MIN_TIME handle. While the table is
+   set, tog_solve_pn, tog_refill, tog_refill_tables, tog_solve_stream and tog_solve_stream_tables return
+   TOG_ERR_UNSUPPORTED (they would read the descriptor's bounds). */
+int32_t tog_set_trajectory_bounds(tog_handle* h, const double* bnd);
 /* copy a field host->device / device->host (host pointers, sizes per tog_field) */
 int32_t tog_set(tog_handle* h, int32_t field, const double* in);
 int32_t tog_get(tog_handle* h, int32_t field, double* out);

@@ -507,6 +507,22 @@ function tog_set_trajectory_obstacles!(s::BatchediLQRSolver, obs::Union{Nothing,
 end
 
 """
+    tog_set_trajectory_bounds!(solver, bnd)
+
+Per-trajectory state and control limits (include/tog.h). `bnd` is `(nb, B)`: entry `[j, b]` is the limit of the bound
+row with ordinal `j` for trajectory `b`; `j` runs over the kept rows of every `BoundConstraint` of the problem's
+sets, in set order, then constraint order, then `[x_max; u_max; x_min; u_min]` (finite entries under `trim`, no `u`
+rows in the terminal knot's set). `nothing` restores the problem's values. Infeasible-start and minimum-time
+solvers refuse it; while it is set, projected Newton and the streamed solves are refused.
+"""
+function tog_set_trajectory_bounds!(s::BatchediLQRSolver, bnd::Union{Nothing,Matrix{Float64}})
+    bnd === nothing || size(bnd, 2) == s.B || throw(ArgumentError("bnd must be (nb, B)"))
+    togcheck(ccall((:tog_set_trajectory_bounds, libtog), Int32, (Ptr{Cvoid}, Ptr{Float64}),
+                   s.handle, bnd === nothing ? C_NULL : bnd))
+    return nothing
+end
+
+"""
     tog_finished(solver) -> Vector{Int32}
     tog_get_slots(solver, field, slots, width) -> Matrix{Float64}   # width: the field's doubles per trajectory
     tog_refill!(solver, slots, x0, U, X = nothing)

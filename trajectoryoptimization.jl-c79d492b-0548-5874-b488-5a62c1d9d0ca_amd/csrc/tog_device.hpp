@@ -107,6 +107,11 @@ struct DevProblem {
   // obs_ld = 4 no doubles per trajectory; each entry is 32 bytes and 32-byte aligned.
   const double* obs;
   int obs_ld, obs_pad;
+  // Per-trajectory bounds (tog_set_trajectory_bounds; null: the rows' own limits): the limit `a` of every bound
+  // row (ROW_XMAX, ROW_UMAX, ROW_XMIN, ROW_UMIN), laid out (nb, B), indexed by the row's ordinal, which the row
+  // keeps in ConRow::b (no reader of a bound row uses b, c or r). bnd_ld = nb doubles per trajectory.
+  const double* bnd;
+  int bnd_ld, bnd_pad;
 };
 
 // Read-only device tables seen through the constant address space. The row tables are read at the
@@ -203,7 +208,7 @@ struct DevBuffers {
   int cost_diag;       // DevProblem::diag_cost (host copy: kernel variants that inline the diagonal cost)
   int tv;              // bit 0: a per-knot cost table (DevProblem::kc: a time-varying Objective, or per-trajectory
                        // cost data beside the replicated shared cost): the team backward kernels' per-knot-cost variants;
-                       // bit 1: per-trajectory costs, goals or obstacles (DevProblem::lin, term, goal, obs): the PT variants of
+                       // bit 1: per-trajectory costs, goals, obstacles or bounds (DevProblem::lin, term, goal, obs, bnd): the PT variants of
                        // the expansion kernels, and the rollouts' run-time-structure (DC = 0) variants
   int rows_lds;        // LDS bytes of a block's copy of the row tables (bulk k_ls_spec; 0: global tables)
   int ls_first;       // width of the first speculative round (>= nc: one round)
@@ -1368,9 +1373,11 @@ __device__ __forceinline__ TermView term_at(const DevProblem* P, long long b) {
 }
 // A loaded constraint row as trajectory b sees it: a goal row takes its target from the goal table
 // (DevProblem::goal), a circle or sphere row its centre and radius from the obstacle table (DevProblem::obs, one
-// 32-byte entry at the row's ordinal). Applied after the row is loaded (from the global tables or an LDS copy of
-// them) and after uniform_row: type and idx are wave-uniform there, the data are per lane, never wave-uniform
-// (the team kernels hold several trajectories in a wave).
+// 32-byte entry at the row's ordinal), a bound row its limit from the bound table (DevProblem::bnd, one double at
+// the row's ordinal, which the row keeps in b). Applied after the row is loaded (from the global tables or an LDS
+// copy of them) and after uniform_row: type and idx are wave-uniform there, the data are per lane, never
+// wave-uniform (the team kernels hold several trajectories in a wave; in k_expand_u's 4-lane teams the lanes of a
+// wave also hold different rows, so there the type and the ordinal are per lane too).
 typedef double obs_entry __attribute__((ext_vector_type(4)));  // [x0, y0, z0, r]
 template <bool PT = true>
 __device__ __forceinline__ ConRow traj_row(const DevProblem* P, long long b, ConRow r) {
@@ -1381,6 +1388,14 @@ __device__ __forceinline__ ConRow traj_row(const DevProblem* P, long long b, Con
     r.b = e.y;
     r.c = e.z;
     r.r = e.w;
+  }
+  // (one wave-uniform test of the table, then a load on every lane and a select: a per-lane branch around the load,
+  // in the kernels whose lanes walk different knots, doubled their scratch on the quadrotor; a row
+  // of another type reads entry 0, which exists whenever the table does)
+  if (PT && P->bnd) {
+    const bool isb = (unsigned)r.type <= (unsigned)ROW_UMIN;
+    const double v = as_global(P->bnd)[(size_t)b * P->bnd_ld + (isb ? (int)r.b : 0)];
+    r.a = isb ? v : r.a;
   }
   return r;
 }

@@ -153,6 +153,10 @@ struct tog_handle {
   // circle (0) or sphere (1) of each obstacle ordinal of the descriptor's sets table (no = size)
   double* d_obs = nullptr;
   std::vector<char> obs_kind;
+  // per-trajectory bounds (tog_set_trajectory_bounds; DevProblem::bnd): the device table (nb, B), and per bound-row
+  // ordinal of the descriptor's sets table whether its constraint is trimmed (nb = size)
+  double* d_bnd = nullptr;
+  std::vector<char> bnd_trimmed;
   // Streamed solves (tog_finished / tog_get_slots / tog_refill / tog_solve_stream), allocated on first use and
   // freed in tog_destroy; everything is ordered on the handle's stream.
   // d_slot_job (B): the job a slot holds whose end has not been listed yet (-1: empty, or listed by
@@ -243,27 +247,42 @@ static const ModelOps* ops_for(int model, bool infeasible, bool min_time, const 
 
 // Flatten the ordered constraint sets into per-knot rows (src/constraint_sets.jl:64-131).
 static int build_rows(const tog_problem_desc* d, int slack, int pcap, int has_con, std::vector<ConRow>& rows,
-                      std::vector<int>& off, std::vector<int>& cnt, std::vector<char>* obs_kind = nullptr) {
+                      std::vector<int>& off, std::vector<int>& cnt, std::vector<char>* obs_kind = nullptr,
+                      std::vector<char>* bnd_trimmed = nullptr) {
   const int n = d->n, m = d->m, N = d->N;
   const int mt = (d->flags & TOG_PROB_MIN_TIME) ? 1 : 0;  // h, the last control
   off.assign(N, 0);
   cnt.assign(N, 0);
   // the ordinal of every circle and sphere (tog_set_trajectory_obstacles' table index, kept in ConRow::idx)
   std::vector<int> set_first(d->n_sets > 0 ? d->n_sets : 0, 0), obs_base;
+  tog_traj::BoundPlan bplan;
   {
     std::vector<int> ncon, ctype, ccount;
+    std::vector<const double*> cdata;
     for (int s = 0; s < d->n_sets; s++) {
       set_first[s] = (int)ctype.size();
       ncon.push_back(d->sets[s].n_con);
       for (int c = 0; c < d->sets[s].n_con; c++) {
         ctype.push_back(d->sets[s].con[c].type);
         ccount.push_back(d->sets[s].con[c].count);
+        cdata.push_back(d->sets[s].con[c].data);
       }
     }
     std::vector<char> kind;
     tog_traj::obstacle_ordinals(ncon.data(), d->n_sets, ctype.data(), ccount.data(), TOG_CON_CIRCLES, TOG_CON_SPHERES,
                                 obs_base, kind);
     if (obs_kind) *obs_kind = kind;
+    // the ordinal of every kept bound row (tog_set_trajectory_bounds' table index, kept in ConRow::b, which no
+    // reader of a bound row uses: DESIGN.md §8). A set that only the terminal knot uses has no control rows.
+    std::vector<char> set_term(d->n_sets > 0 ? d->n_sets : 0, 0);
+    if (d->knot_set && N > 0 && d->knot_set[N - 1] >= 0 && d->knot_set[N - 1] < d->n_sets) {
+      set_term[d->knot_set[N - 1]] = 1;
+      for (int k = 0; k < N - 1; k++)
+        if (d->knot_set[k] == d->knot_set[N - 1]) set_term[d->knot_set[N - 1]] = 0;
+    }
+    tog_traj::bound_ordinals(ncon.data(), set_term.data(), d->n_sets, ctype.data(), ccount.data(), cdata.data(),
+                             TOG_CON_BOUND, n, m, slack, mt, bplan);
+    if (bnd_trimmed) *bnd_trimmed = bplan.trimmed;
   }
   for (int k = 0; k < N; k++) {
     off[k] = (int)rows.size();
@@ -285,18 +304,24 @@ static int build_rows(const tog_problem_desc* d, int slack, int pcap, int has_co
           // combined bound reaches u[1:m+1], mintime_constraints, minimum_time.jl:125-141)
           // (trim=false: the model's controls and, on a minimum-time problem, the time step h = u[m-1])
           const bool keep = (con.count == 1);
-          const int mb = keep ? m - slack - mt : m;
-          auto u_row = [&](int i) { return i < mb || (keep && mt && i == m - 1); };
+          auto u_row = [&](int i) { return tog_traj::bound_u_kept(i, keep, m, slack, mt); };
+          // (ord: the row's ordinal, counted from its block's first over the kept rows; the x blocks of a set
+          // that stage knots and the terminal knot share keep the stage rows' ordinals)
+          const int* ob = &bplan.base[4 * (size_t)(set_first[si] + c)];
+          int ord = ob[0];
           for (int i = 0; i < n; i++)
-            if (keep || isfinite(D[i])) rows.push_back({ROW_XMAX, i, D[i], 0, 0, 0});
+            if (keep || isfinite(D[i])) rows.push_back({ROW_XMAX, i, D[i], (double)ord++, 0, 0});
+          ord = ob[1];
           if (!term)
             for (int i = 0; i < m; i++)
-              if (u_row(i) && (keep || isfinite(D[2 * n + i]))) rows.push_back({ROW_UMAX, i, D[2 * n + i], 0, 0, 0});
+              if (u_row(i) && (keep || isfinite(D[2 * n + i]))) rows.push_back({ROW_UMAX, i, D[2 * n + i], (double)ord++, 0, 0});
+          ord = ob[2];
           for (int i = 0; i < n; i++)
-            if (keep || isfinite(D[n + i])) rows.push_back({ROW_XMIN, i, D[n + i], 0, 0, 0});
+            if (keep || isfinite(D[n + i])) rows.push_back({ROW_XMIN, i, D[n + i], (double)ord++, 0, 0});
+          ord = ob[3];
           if (!term)
             for (int i = 0; i < m; i++)
-              if (u_row(i) && (keep || isfinite(D[2 * n + m + i]))) rows.push_back({ROW_UMIN, i, D[2 * n + m + i], 0, 0, 0});
+              if (u_row(i) && (keep || isfinite(D[2 * n + m + i]))) rows.push_back({ROW_UMIN, i, D[2 * n + m + i], (double)ord++, 0, 0});
           break;
         }
         case TOG_CON_GOAL: {  // count: rows x[1:count] - xf (the goal's inds); 0 = n
@@ -1206,7 +1231,7 @@ static int32_t create_single(tog_handle* h, const tog_problem_desc* d, const tog
   h->nq = n + m + n * n + m * m + m * n;
 
   HostRows hr;
-  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, hr.rows, hr.off, hr.cnt, &h->obs_kind);
+  int rc = build_rows(d, ops->slack, ops->pcap, ops->has_con, hr.rows, hr.off, hr.cnt, &h->obs_kind, &h->bnd_trimmed);
   if (rc) return rc;
   h->nrows = (int)hr.rows.size();
   h->pmax = 0;
@@ -1566,7 +1591,8 @@ static int32_t traj_apply(tog_handle* h) {
   DevProblem& P = h->hostP;
   // (the obstacle table needs no per-knot cost table: cost_at returns the shared cost without one, and the
   // backward kernels read no constraint row, so an obstacle-only handle sets variant bit 1 alone)
-  const bool cost = h->d_lin || h->d_term || h->d_goal, any = cost || h->d_obs;
+  // (nor does the bound table: it replaces a row's limit, which the same readers take through traj_row)
+  const bool cost = h->d_lin || h->d_term || h->d_goal, any = cost || h->d_obs || h->d_bnd;
   if (cost && !h->kc0 && !h->d_kc_rep) {
     const std::vector<double> t = tog_traj::replicate_row(h->kc_row, h->N - 1);
     int32_t rc = dalloc(h, &h->d_kc_rep, t.size());
@@ -1580,6 +1606,8 @@ static int32_t traj_apply(tog_handle* h) {
   P.goal_ld = h->n;
   P.obs = h->d_obs;
   P.obs_ld = (int)tog_traj::obs_width((int)h->obs_kind.size());
+  P.bnd = h->d_bnd;
+  P.bnd_ld = (int)h->bnd_trimmed.size();
   h->buf.tv = ((h->tv0 || cost) ? 1 : 0) | (any ? 2 : 0);  // (bit 1: the per-trajectory kernel variants)
   HIPCHECK(hipStreamSynchronize(h->stream));
   HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
@@ -1677,6 +1705,34 @@ int32_t tog_set_trajectory_obstacles(tog_handle* h, const double* obs) {
   } else {
     rc = traj_table(h, &h->d_obs, nullptr, 0);
   }
+  const int32_t ra = traj_apply(h);
+  return rc ? rc : ra;
+}
+
+int32_t tog_set_trajectory_bounds(tog_handle* h, const double* bnd) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (is_multi(h)) {
+    const size_t w = h->parts[0]->bnd_trimmed.size();
+    const tog_handle* p0 = h->parts[0];
+    // (the whole table is checked before any part takes its slice: a refused table leaves every part's in place)
+    if (bnd && !p0->ops->slack && !p0->ops->min_time && w > 0) {
+      long long Ball = 0;
+      for (const tog_handle* p : h->parts) Ball += p->B;
+      const std::string err = tog_traj::bound_table_check(bnd, p0->bnd_trimmed, Ball);
+      if (!err.empty()) return fail(TOG_ERR_ARG, err);
+    }
+    return each_part(h, [&](tog_handle* p, size_t o) {
+      return tog_set_trajectory_bounds(p, tog_traj::part_slice(bnd, o, w));
+    });
+  }
+  if (h->ops->slack || h->ops->min_time) return fail(TOG_ERR_UNSUPPORTED, tog_traj::bounds_refuse_text());
+  if (h->bnd_trimmed.empty()) return fail(TOG_ERR_ARG, tog_traj::bounds_none_text());
+  if (bnd) {
+    const std::string err = tog_traj::bound_table_check(bnd, h->bnd_trimmed, h->B);
+    if (!err.empty()) return fail(TOG_ERR_ARG, err);  // (the table in place stays)
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  const int32_t rc = traj_table(h, &h->d_bnd, bnd, bnd ? h->bnd_trimmed.size() * (size_t)h->B : 0);
   const int32_t ra = traj_apply(h);
   return rc ? rc : ra;
 }
@@ -2029,6 +2085,8 @@ static int32_t stream_refuse(const tog_handle* h, const char* who) {
 // last job's obstacles (streaming obstacle sweeps is not built)
 static int32_t obs_refuse(const tog_handle* h, const char* who) {
   if (h && !is_multi(h) && h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text(who));
+  // likewise the bound table: a refilled slot would keep the last job's limits
+  if (h && !is_multi(h) && h->d_bnd) return fail(TOG_ERR_UNSUPPORTED, tog_traj::bounds_set_text(who));
   return TOG_OK;
 }
 
@@ -2510,6 +2568,7 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
     return fail(TOG_ERR_UNSUPPORTED, "tog_solve_pn: per-trajectory costs or goals are set (projected Newton reads the "
                                      "shared objective and goal; clear them with NULL tables first)");
   if (h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text("tog_solve_pn"));
+  if (h->d_bnd) return fail(TOG_ERR_UNSUPPORTED, tog_traj::bounds_set_text("tog_solve_pn"));
   const bool optimal = opts->solve_type == 1;
   if (opts->n_steps < 0) return fail(TOG_ERR_ARG, "n_steps must be >= 0");
   if (!h->ops->pn) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");

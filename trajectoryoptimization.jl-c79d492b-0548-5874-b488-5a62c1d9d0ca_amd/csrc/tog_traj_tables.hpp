@@ -103,6 +103,88 @@ inline std::string obstacles_set_text(const char* who) {
                             "data; clear the table with tog_set_trajectory_obstacles(h, NULL) first)";
 }
 
+// ---- per-trajectory bounds (tog_set_trajectory_bounds): the limit `a` of the bound rows.
+// Every bound row that build_rows keeps over the descriptor's sets table has an ordinal: sets in order,
+// constraints in their set's order, within a bound constraint the kept rows in the order [x_max; u_max; x_min;
+// u_min]. A set used at many knots (or at none) contributes once; a set that only the terminal knot uses
+// contributes no control rows (the terminal knot has none). The row keeps its ordinal in ConRow::b.
+// u_kept: whether build_rows keeps the control row i of a bound constraint at a stage knot, finiteness aside
+// (keep: trim = false; slack, mt: the slack controls and the time step of an infeasible-start / minimum-time
+// problem, which an untrimmed bound leaves out or adds)
+inline bool bound_u_kept(int i, bool keep, int m, int slack, int mt) {
+  const int mb = keep ? m - slack - mt : m;
+  return i < mb || (keep && mt && i == m - 1);
+}
+struct BoundPlan {
+  // per constraint (all sets' constraints in one run): the ordinal of the first kept row of each block
+  // [x_max, u_max, x_min, u_min] (-1: not a bound constraint)
+  std::vector<int> base;
+  std::vector<char> trimmed;  // per ordinal: 1 when the row exists because its bound is finite (a trimmed constraint)
+  int nb = 0;
+};
+// set_ncon[s]: constraints of set s; set_term[s]: 1 when only the terminal knot uses set s; con_type /
+// con_count / con_data: type, count (0: trim = true, 1: trim = false) and data [x_max(n), x_min(n), u_max(m),
+// u_min(m)] of each constraint. Returns nb.
+inline int bound_ordinals(const int* set_ncon, const char* set_term, int n_sets, const int* con_type,
+                          const int* con_count, const double* const* con_data, int bound_type, int n, int m,
+                          int slack, int mt, BoundPlan& plan) {
+  plan.base.clear();
+  plan.trimmed.clear();
+  int i = 0, nb = 0;
+  auto finite = [](double v) { return v == v && v - v == 0.0; };
+  for (int s = 0; s < n_sets; s++)
+    for (int c = 0; c < set_ncon[s]; c++, i++) {
+      if (con_type[i] != bound_type) {
+        plan.base.insert(plan.base.end(), 4, -1);
+        continue;
+      }
+      const bool keep = con_count[i] == 1;
+      const double* D = con_data[i];
+      // block order [x_max; u_max; x_min; u_min]; data offsets 0, 2n, n, 2n + m
+      const int off[4] = {0, 2 * n, n, 2 * n + m};
+      for (int blk = 0; blk < 4; blk++) {
+        const bool isu = blk & 1;
+        plan.base.push_back(nb);
+        if (isu && set_term[s]) continue;
+        for (int j = 0; j < (isu ? m : n); j++) {
+          if (isu && !bound_u_kept(j, keep, m, slack, mt)) continue;
+          if (!keep && !finite(D[off[blk] + j])) continue;
+          plan.trimmed.push_back(keep ? 0 : 1);
+          nb++;
+        }
+      }
+    }
+  plan.nb = nb;
+  return nb;
+}
+// (nb, B) limits: empty when they can replace the rows' own, else why not. A NaN anywhere, or a non-finite value
+// at a row of a trimmed constraint (the row exists because the bound is finite; an untrimmed row may be
+// infinite, as in the descriptor).
+inline std::string bound_table_check(const double* bnd, const std::vector<char>& trimmed, long long B) {
+  const size_t nb = trimmed.size();
+  for (long long b = 0; b < B; b++)
+    for (size_t j = 0; j < nb; j++) {
+      const double v = bnd[(size_t)b * nb + j];
+      if (v != v)
+        return "tog_set_trajectory_bounds: NaN at row " + std::to_string(j) + " of trajectory " + std::to_string(b);
+      if (trimmed[j] && v - v != 0.0)
+        return "tog_set_trajectory_bounds: infinite bound at row " + std::to_string(j) + " of trajectory " +
+               std::to_string(b) + " (a row of a trimmed constraint exists because its bound is finite)";
+    }
+  return std::string();
+}
+inline std::string bounds_none_text() { return "tog_set_trajectory_bounds: the problem has no bound row"; }
+// infeasible-start and minimum-time handles
+inline std::string bounds_refuse_text() {
+  return "tog_set_trajectory_bounds: infeasible-start and minimum-time problems keep the batch's bounds (their "
+         "combined bounds are built from the descriptor)";
+}
+// the entry points whose kernels or staging read the descriptor's bounds
+inline std::string bounds_set_text(const char* who) {
+  return std::string(who) + ": per-trajectory bounds are set (this call reads the descriptor's bounds; clear the "
+                            "table with tog_set_trajectory_bounds(h, NULL) first)";
+}
+
 // a host array's slice for the part of a multi-device handle that starts at trajectory `off` (the batch axis is
 // the outermost one; a null array stays null)
 inline const double* part_slice(const double* a, size_t off, size_t width) { return a ? a + off * width : nullptr; }

@@ -123,6 +123,11 @@ class BatchHandle:
             self.set_trajectory_obstacles(obs)
         elif getattr(self, "_traj_obstacles", False):
             self.set_trajectory_obstacles(None)
+        bnd = prob.trajectory_bounds() if hasattr(prob, "trajectory_bounds") else None
+        if bnd is not None:
+            self.set_trajectory_bounds(bnd)
+        elif getattr(self, "_traj_bounds", False):
+            self.set_trajectory_bounds(None)
 
     def set_trajectory_costs(self, lin=None, term=None):
         """tog_set_trajectory_costs. lin: (B, n+m+1) rows [q; r; c], or (B, N-1, n+m+1) with a row per stage
@@ -169,6 +174,19 @@ class BatchHandle:
             raise ValueError(f"obs must be ({self.B}, no, 4), got {obs.shape}")
         abi.check(self.lib, self.lib.tog_set_trajectory_obstacles(self.h, abi.as_dp(obs)))
         self._traj_obstacles = True
+
+    def set_trajectory_bounds(self, bnd=None):
+        """tog_set_trajectory_bounds. bnd: (B, nb) limits of every kept bound row in the ABI's ordinal order
+        (Problem.trajectory_bounds); None: the descriptor's."""
+        if bnd is None:
+            abi.check(self.lib, self.lib.tog_set_trajectory_bounds(self.h, C.cast(None, C.POINTER(C.c_double))))
+            self._traj_bounds = False
+            return
+        bnd = np.ascontiguousarray(bnd, dtype=np.float64)
+        if bnd.ndim != 2 or bnd.shape[0] != self.B:
+            raise ValueError(f"bnd must be ({self.B}, nb), got {bnd.shape}")
+        abi.check(self.lib, self.lib.tog_set_trajectory_bounds(self.h, abi.as_dp(bnd)))
+        self._traj_bounds = True
 
     def download_state(self, prob):
         prob._X[...] = self.get(abi.FIELD_X)

@@ -591,21 +591,80 @@ class BoundConstraint(_Constraint):
     ``trim=false`` keeps every row (an infinite bound then evaluates to -Inf and the AL terms to NaN, as
     in the reference). At the terminal knot the untrimmed rows are x_max and x_min (the reference's
     untrimmed ``x_all`` mask, ``[trues(n); falses(m); trues(m); falses(m)]``, has the wrong length unless
-    n == m; its evident intent is taken)."""
+    n == m; its evident intent is taken).
+
+    Any of the four limits may be ``(B, n)`` / ``(B, m)``: the limits of each trajectory
+    (tog_set_trajectory_bounds). The four are then all held per trajectory, the descriptor carries
+    trajectory 0's, and under ``trim=True`` every trajectory must have the same finite entries (the rows are
+    the batch's, their limits the trajectory's)."""
 
     label = "bound"
 
     def __init__(self, n, m, x_min=-math.inf, x_max=math.inf, u_min=-math.inf, u_max=math.inf, trim=True):
         self.n, self.m = n, m
-        self.u_max, self.u_min = _validate_bounds(u_max, u_min, m)
-        self.x_max, self.x_min = _validate_bounds(x_max, x_min, n)
         self.trim = bool(trim)
+        given = dict(x_min=x_min, x_max=x_max, u_min=u_min, u_max=u_max)
+        Bs = sorted({np.shape(v)[0] for v in given.values() if np.ndim(v) == 2})
+        if any(np.ndim(v) > 2 for v in given.values()) or len(Bs) > 1:
+            raise ValueError("BoundConstraint: per-trajectory limits must be (B, n) / (B, m) with one B, got "
+                             + ", ".join(f"{k}{np.shape(v)}" for k, v in given.items() if np.ndim(v) >= 2))
+        if Bs:
+            def at(v, b):
+                return v[b] if np.ndim(v) == 2 else v
+
+            ux, xx = [], []
+            for b in range(Bs[0]):
+                try:
+                    ux.append(_validate_bounds(at(u_max, b), at(u_min, b), m))
+                    xx.append(_validate_bounds(at(x_max, b), at(x_min, b), n))
+                except ValueError as e:
+                    raise ValueError(f"BoundConstraint, trajectory {b}: {e}") from None
+            self.u_max, self.u_min = np.stack([t[0] for t in ux]), np.stack([t[1] for t in ux])
+            self.x_max, self.x_min = np.stack([t[0] for t in xx]), np.stack([t[1] for t in xx])
+        else:
+            self.u_max, self.u_min = _validate_bounds(u_max, u_min, m)
+            self.x_max, self.x_min = _validate_bounds(x_max, x_min, n)
+        first = {k: (getattr(self, k)[0] if Bs else getattr(self, k)) for k in ("x_max", "u_max", "x_min", "u_min")}
         if self.trim:
-            self.active = dict(x_max=np.isfinite(self.x_max), u_max=np.isfinite(self.u_max),
-                               x_min=np.isfinite(self.x_min), u_min=np.isfinite(self.u_min))
+            self.active = {k: np.isfinite(v) for k, v in first.items()}
+            for k in first if Bs else ():
+                diff = np.argwhere(np.isfinite(getattr(self, k)) != self.active[k])
+                if len(diff):
+                    b, i = (int(t) for t in diff[0])
+                    raise ValueError(f"BoundConstraint: trim=True keeps a row per finite limit, so every trajectory "
+                                     f"must have the same finite entries; {k}[{i}] of trajectory {b} is "
+                                     f"{getattr(self, k)[b, i]}, trajectory 0's is {first[k][i]}")
         else:
             self.active = dict(x_max=np.ones(n, bool), u_max=np.ones(m, bool), x_min=np.ones(n, bool),
                                u_min=np.ones(m, bool))
+
+    @property
+    def batched(self):
+        return self.x_max.ndim == 2
+
+    def _limits(self, pick):
+        return dict(x_min=pick(self.x_min), x_max=pick(self.x_max), u_min=pick(self.u_min), u_max=pick(self.u_max))
+
+    def for_traj(self, b):
+        """trajectory b's plain bound constraint"""
+        return BoundConstraint(self.n, self.m, trim=self.trim, **self._limits(lambda v: v[b])) if self.batched else self
+
+    def slice(self, lo, hi):
+        if not self.batched:
+            return self
+        return BoundConstraint(self.n, self.m, trim=self.trim, **self._limits(lambda v: v[lo:hi]))
+
+    def bound_rows(self, B, kind="stage"):
+        """(B, rows) limits of the kept rows in the constraint vector's order [x_max; u_max; x_min; u_min] (the
+        terminal knot's: [x_max; x_min]): the ABI's per-trajectory layout"""
+        a = self.active
+        names = ("x_max", "u_max", "x_min", "u_min") if kind == "stage" else ("x_max", "x_min")
+        cols = []
+        for k in names:
+            v = getattr(self, k)
+            v = v if self.batched else np.broadcast_to(v, (B,) + v.shape)
+            cols.append(v[:, a[k]])
+        return np.concatenate(cols, axis=1)
 
     def length(self, kind="stage"):
         a = self.active
@@ -616,11 +675,17 @@ class BoundConstraint(_Constraint):
     def evaluate(self, x, u=None):  # src/constraints.jl:212-227
         a = self.active
         x = np.asarray(x, dtype=np.float64)
+        x_max, x_min, u_max, u_min = self._first()
         if u is None:
-            return np.concatenate([(x - self.x_max)[a["x_max"]], (self.x_min - x)[a["x_min"]]])
+            return np.concatenate([(x - x_max)[a["x_max"]], (x_min - x)[a["x_min"]]])
         u = np.asarray(u, dtype=np.float64)[: self.m]  # u[con.inds[2]] (constraint_sets.jl:106-110)
-        return np.concatenate([(x - self.x_max)[a["x_max"]], (u - self.u_max)[a["u_max"]],
-                               (self.x_min - x)[a["x_min"]], (self.u_min - u)[a["u_min"]]])
+        return np.concatenate([(x - x_max)[a["x_max"]], (u - u_max)[a["u_max"]],
+                               (x_min - x)[a["x_min"]], (u_min - u)[a["u_min"]]])
+
+    def _first(self):
+        """[x_max, x_min, u_max, u_min] of the plain constraint, or of trajectory 0"""
+        f = (lambda v: v[0]) if self.batched else (lambda v: v)
+        return f(self.x_max), f(self.x_min), f(self.u_max), f(self.u_min)
 
     def jacobian(self, x, u=None):  # src/constraints.jl:229-237
         n, m = self.n, self.m
@@ -637,7 +702,8 @@ class BoundConstraint(_Constraint):
         # (update_constraint_set_jacobians, constraint_sets.jl:135-150), so the rows are those of the model
         # controls, trimmed or not (the device's build_rows and the oracle's con_init skip the slack entries)
         pad = np.full(0 if m is None else m - self.m, np.inf)
-        data = np.concatenate([self.x_max, self.x_min, self.u_max, pad, self.u_min, -pad])
+        x_max, x_min, u_max, u_min = self._first()
+        data = np.concatenate([x_max, x_min, u_max, pad, u_min, -pad])
         return (abi.CON_BOUND, 0 if self.trim else 1, data)
 
 
@@ -933,7 +999,7 @@ def _copy_constraints(cons):
 
 
 # the constraints that can hold data per trajectory (batched, for_traj)
-_PER_TRAJECTORY = (GoalConstraint, CircleConstraints, SphereConstraints)
+_PER_TRAJECTORY = (GoalConstraint, CircleConstraints, SphereConstraints, BoundConstraint)
 
 # ----------------------------------------------------------------------------- problem
 
@@ -1050,9 +1116,25 @@ class Problem:
         return any(isinstance(c, (CircleConstraints, SphereConstraints)) and c.batched
                    for cs in self.constraints.C for c in cs)
 
+    def trajectory_bounds(self):
+        """(B, nb) limits of every kept bound row in the ABI's ordinal order (tog_set_trajectory_bounds: sets in
+        the descriptor's order, constraints in their set's order, then [x_max; u_max; x_min; u_min] over the kept
+        rows; the terminal knot's set has no u rows; an object in two distinct sets is emitted once per set), or
+        None when no bound constraint holds per-trajectory data."""
+        if not self.has_trajectory_bounds():
+            return None
+        sets, knot_set = self._abi_sets()
+        term = knot_set[self.N - 1]
+        rows = [c.bound_rows(self.B, "terminal" if s == term else "stage")
+                for s, cs in enumerate(sets) for c in cs if isinstance(c, BoundConstraint)]
+        return np.ascontiguousarray(np.concatenate(rows, axis=1))
+
+    def has_trajectory_bounds(self) -> bool:
+        return any(isinstance(c, BoundConstraint) and c.batched for cs in self.constraints.C for c in cs)
+
     def has_trajectory_data(self) -> bool:
         return (isinstance(self.obj, BatchObjective) or self.trajectory_goals() is not None
-                or self.has_trajectory_obstacles())
+                or self.has_trajectory_obstacles() or self.has_trajectory_bounds())
 
     def check_trajectory_data(self):
         """shapes of the per-trajectory data against the batch (ValueError)"""
@@ -1071,6 +1153,9 @@ class Problem:
                     if have != B:
                         raise ValueError(f"{type(c).__name__} holds the obstacles of {have} trajectories, the "
                                          f"problem {B} trajectories")
+                if isinstance(c, BoundConstraint) and c.batched and c.x_max.shape[0] != B:
+                    raise ValueError(f"BoundConstraint holds the limits of {c.x_max.shape[0]} trajectories, the "
+                                     f"problem {B} trajectories")
 
     def trajectory(self, b: int) -> "Problem":
         """The plain B = 1 problem of trajectory b: its objective, goal, x0, U, X."""
@@ -1093,7 +1178,7 @@ class Problem:
 
     def batch_slice(self, lo: int, hi: int) -> "Problem":
         """Trajectories [lo, hi) as a batch of their own: their x0, U, X, and their members of a BatchObjective
-        and of per-trajectory goals and obstacles (what a streamed solve's handle is created with, solve_stream)."""
+        and of per-trajectory goals, obstacles and bounds (what a streamed solve's handle is created with, solve_stream)."""
         if not 0 <= lo < hi <= self.B:
             raise IndexError(f"trajectories [{lo}, {hi}) of {self.B}")
         p = _copy.copy(self)
@@ -1201,7 +1286,7 @@ def max_violation(prob: Problem) -> float:
                 vals_e, vals = [], []
                 for c in cs:
                     if isinstance(c, _PER_TRAJECTORY):
-                        c = c.for_traj(b)  # (a goal, or obstacles, per trajectory)
+                        c = c.for_traj(b)  # (a goal, obstacles or limits per trajectory)
                     v = c.evaluate(X[k]) if term else c.evaluate(X[k], U[k])
                     if len(v) == 0:
                         continue
@@ -1221,6 +1306,15 @@ def max_violation(prob: Problem) -> float:
 # ----------------------------------------------------------------------------- infeasible start
 
 
+def _refuse_trajectory_bounds(prob, who):
+    """The infeasible-start and minimum-time problems build their combined bounds from one set of limits (and
+    their handles refuse tog_set_trajectory_bounds): a problem with per-trajectory limits is refused here."""
+    if prob.has_trajectory_bounds():
+        raise ValueError(f"{who}: the problem has per-trajectory bounds (BoundConstraint limits (B, n) / (B, m)); "
+                         "its combined bounds are built from one set of limits. Transform one trajectory at a time "
+                         "through Problem.trajectory(b)")
+
+
 def infeasible_problem(prob: Problem, R_inf: float = 1.0) -> Problem:
     """``infeasible_problem(prob, R_inf)`` (src/solvers/altro/infeasible.jl:2-33).
 
@@ -1232,6 +1326,7 @@ def infeasible_problem(prob: Problem, R_inf: float = 1.0) -> Problem:
     The terminal set is kept. The state trajectory X is kept; the slack controls are filled on
     the device by ``slack_controls`` (infeasible.jl:63-80) when the solver is set up.
     """
+    _refuse_trajectory_bounds(prob, "infeasible_problem")
     n, m, N = prob.model.n, prob.model.m, prob.N
     term = prob.obj.terminal
 
@@ -1332,6 +1427,7 @@ def minimum_time_problem(prob: Problem, R_min_time: float = 1.0, dt_max: float =
     ``add_min_time_controls``, the objective MinTimeCost (the quadratic costs zero-padded to the
     augmented sizes plus R_min_time h², on the device), ``mintime_constraints``,
     U = [U; √dt], X = [X; √dt], x0 = [x0; 0]."""
+    _refuse_trajectory_bounds(prob, "minimum_time_problem")
     n, m, N = prob.model.n, prob.model.m, prob.N
     term = prob.obj.terminal
 

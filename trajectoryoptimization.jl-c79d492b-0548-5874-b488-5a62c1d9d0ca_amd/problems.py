@@ -404,6 +404,30 @@ def config_quad_maze_obstacles(B=8192, offset=0, N=201):
     return out, opts
 
 
+QUAD_BOUNDS_U_MAX = (4.0, 10.0)  # config_quadrotor_bounds: the range of a trajectory's thrust limit
+QUAD_BOUNDS_U_MIN = (0.0, 1.0)   # and of its idle thrust
+
+
+def config_quadrotor_bounds(B=8192, offset=0):
+    """Config 3 with the thrust limits of each trajectory its own (tog_set_trajectory_bounds): an actuator-sizing
+    sweep. u_max[b] ~ U(4, 10) and u_min[b] ~ U(0, 1), one value of each per trajectory for all four rotors (seed
+    5000+b, u_max drawn first); config 3's own limits are [0, 15], hover is 1.23 per rotor. x0, U0 and the
+    options are config 3's. In the oracle each of the first 8 trajectories ends AL_CONVERGED with a control-bound
+    row active (|c| below the constraint tolerance); tests/test_trajectory_bounds.py holds them to it. (When the
+    ranges were chosen the first 64 were run once: all converged, in 26 to 1131 steps.)"""
+    prob, opts = config_quadrotor(B=B, offset=offset)
+    N, n, m = prob.N, 13, 4
+    Z = _per_traj_rng(5000 + offset, B, lambda r: np.array([r.uniform(*QUAD_BOUNDS_U_MAX), r.uniform(*QUAD_BOUNDS_U_MIN)]))
+    bnd0 = next(c for c in prob.constraints[0] if isinstance(c, BoundConstraint))
+    bnd = BoundConstraint(n, m, u_min=np.repeat(Z[:, 1:2], m, axis=1), u_max=np.repeat(Z[:, 0:1], m, axis=1))
+    cons = Constraints(N)
+    for k in range(N):
+        cons[k] = ConstraintSet(bnd if c is bnd0 else c for c in prob.constraints[k])
+    out = Problem(prob.model, prob.obj, constraints=cons, x0=prob.x0, xf=prob.xf, N=N, dt=prob.dt)
+    out._U[...] = prob._U
+    return out, opts
+
+
 def config_kuka(B=4096, offset=0):
     """Config 5: Kuka iiwa (n=14, m=7, N=51), AL-iLQR with the terminal goal and the notebook's options;
     x0[1:7] ~ U(-0.2, 0.2) (seed 4000+b), U0 = the hold trajectory at x0 (the notebook's own
