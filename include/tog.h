@@ -38,7 +38,8 @@ extern "C" {
 /* still 5: the streamed solves (tog_finished, tog_get_slots, tog_refill, tog_refill_tables, tog_solve_stream,
       tog_solve_stream_tables) are new functions only; no struct, enum or existing signature changed;
       likewise tog_rollout_plan (a query for tests) and tog_set_trajectory_obstacles (per-trajectory circle and
-      sphere data) and tog_set_trajectory_bounds (per-trajectory state and control limits) */
+      sphere data), tog_set_trajectory_bounds (per-trajectory state and control limits) and
+      tog_set_trajectory_weights (per-trajectory cost Hessians) */
 #define TOG_ABI_VERSION 5
 
 /* ---------------------------------------------------------------- status */
@@ -168,10 +169,11 @@ typedef struct tog_constraint_set {
    (src/constraint_sets.jl:157-206). One problem, B independent trajectories
    that differ in x0 and the initial controls U0 and, once set on the handle, in the
    linear and constant terms of their cost, in their goal, in the centres and radii
-   of their circle and sphere obstacles and in the limits of their bound rows
-   (tog_set_trajectory_costs, tog_set_trajectory_goals, tog_set_trajectory_obstacles,
-   tog_set_trajectory_bounds). The cost Hessians, the dynamics, the user constraints,
-   the number and kind of the obstacles and which bounds have a row are the batch's. */
+   of their circle and sphere obstacles, in the limits of their bound rows and in their
+   cost Hessians Q, R, H and Qf (tog_set_trajectory_costs, tog_set_trajectory_goals,
+   tog_set_trajectory_obstacles, tog_set_trajectory_bounds, tog_set_trajectory_weights).
+   The dynamics, the user constraints, the number and kind of the obstacles and which
+   bounds have a row are the batch's; so is a time-varying stage_costs table. */
 typedef struct tog_problem_desc {
   int32_t model;      /* tog_model_id                       */
   int32_t integrator; /* tog_integrator                     */
@@ -416,6 +418,22 @@ int32_t tog_set_trajectory_obstacles(tog_handle* h, const double* obs);
    set, tog_solve_pn, tog_refill, tog_refill_tables, tog_solve_stream and tog_solve_stream_tables return
    TOG_ERR_UNSUPPORTED (they would read the descriptor's bounds). */
 int32_t tog_set_trajectory_bounds(tog_handle* h, const double* bnd);
+/* Per-trajectory cost weights: the Hessians of the cost. W: (nw, B), host pointer, nw = 2 n^2 + m^2 + m n; the
+   block of trajectory b is [Q (n, n); R (m, m); H (m, n); Qf (n, n)], each matrix column-major with the
+   descriptor's n and m. They replace desc.Q, R, H and Qf for that trajectory; q, r, c, qf and cf stay the
+   descriptor's, or the tables' of tog_set_trajectory_costs. The square-root factors are computed as tog_create
+   computes them, so trajectory b solves bit for bit as a handle of its own with these Hessians would. NULL
+   restores the descriptor's Hessians. Replacement, lifetime and the split on a tog_create_multi handle are as
+   for tog_set_trajectory_costs; a multi-device handle checks the whole table before any part takes its slice.
+   TOG_ERR_ARG, with the trajectory and the matrix named in tog_last_error, for a NaN or an infinity, for a Q, R
+   or Qf that is not symmetric and, on a handle created with options.square_root, for a Hessian that is not
+   positive definite (as tog_create refuses the descriptor's); the table in place stays. On a handle without
+   square_root such Hessians are accepted and the step-level square-root backward pass refuses while they are
+   set. TOG_ERR_UNSUPPORTED on a TOG_PROB_INFEASIBLE or TOG_PROB_MIN_TIME handle and on a handle whose descriptor
+   has a stage_costs table (Hessians per trajectory and per knot are not built). While the table is set,
+   tog_solve_pn, tog_refill, tog_refill_tables, tog_solve_stream and tog_solve_stream_tables return
+   TOG_ERR_UNSUPPORTED (they would read the descriptor's Hessians). */
+int32_t tog_set_trajectory_weights(tog_handle* h, const double* W);
 /* copy a field host->device / device->host (host pointers, sizes per tog_field) */
 int32_t tog_set(tog_handle* h, int32_t field, const double* in);
 int32_t tog_get(tog_handle* h, int32_t field, double* out);

@@ -523,6 +523,25 @@ function tog_set_trajectory_bounds!(s::BatchediLQRSolver, bnd::Union{Nothing,Mat
 end
 
 """
+    tog_set_trajectory_weights!(solver, W)
+
+Per-trajectory cost Hessians (include/tog.h). `W` is `(nw, B)` with `nw = 2n² + m² + mn`: column `b` is
+`[vec(Q); vec(R); vec(H); vec(Qf)]` of trajectory `b` (`Q`, `Qf` n×n, `R` m×m, `H` m×n; `vec` is Julia's
+column-major one). They replace the problem's `Q`, `R`, `H` and `Qf` for that trajectory; `q`, `r`, `c`, `qf`, `cf`
+stay the problem's or the tables' of `tog_set_trajectory_costs!`. `nothing` restores the problem's Hessians.
+`Q`, `R`, `Qf` must be symmetric and, on a square-root solver, positive definite. Infeasible-start and minimum-time
+solvers and solvers of a time-varying objective refuse it; while it is set, projected Newton and the streamed
+solves are refused.
+"""
+function tog_set_trajectory_weights!(s::BatchediLQRSolver, W::Union{Nothing,Matrix{Float64}})
+    nw = 2 * s.n^2 + s.m^2 + s.m * s.n
+    W === nothing || size(W) == (nw, s.B) || throw(ArgumentError("W must be (2n^2 + m^2 + mn, B)"))
+    togcheck(ccall((:tog_set_trajectory_weights, libtog), Int32, (Ptr{Cvoid}, Ptr{Float64}),
+                   s.handle, W === nothing ? C_NULL : W))
+    return nothing
+end
+
+"""
     tog_finished(solver) -> Vector{Int32}
     tog_get_slots(solver, field, slots, width) -> Matrix{Float64}   # width: the field's doubles per trajectory
     tog_refill!(solver, slots, x0, U, X = nothing)

@@ -277,6 +277,7 @@ def load_library(path: os.PathLike | None = None):
     lib.tog_set_trajectory_goals.argtypes = [vp, _dp]
     lib.tog_set_trajectory_obstacles.argtypes = [vp, _dp]
     lib.tog_set_trajectory_bounds.argtypes = [vp, _dp]
+    lib.tog_set_trajectory_weights.argtypes = [vp, _dp]
     lib.tog_get.argtypes = [vp, C.c_int32, _dp]
     lib.tog_get_device_ptr.argtypes = [vp, C.c_int32, C.POINTER(vp)]
     lib.tog_dims.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -346,7 +347,8 @@ def load_library(path: os.PathLike | None = None):
                  "tog_model_free", "tog_generic_cost_load", "tog_generic_cost_dims", "tog_generic_cost_expand", "tog_generic_cost_expand_device",
                  "tog_generic_cost_free", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable",
                  "tog_get_pn_history", "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs",
-                 "tog_set_trajectory_goals", "tog_set_trajectory_obstacles", "tog_set_trajectory_bounds"):
+                 "tog_set_trajectory_goals", "tog_set_trajectory_obstacles", "tog_set_trajectory_bounds",
+                 "tog_set_trajectory_weights"):
         getattr(lib, name).restype = C.c_int32
     if lib.tog_version() != TOG_ABI_VERSION:
         raise RuntimeError("libtog ABI version mismatch")
@@ -368,7 +370,7 @@ EXPORTED_SYMBOLS = (
     "tog_default_altro_options", "tog_solve_altro", "tog_solve_altro_ex", "tog_history_enable", "tog_get_pn_history",
     "tog_batch_stats_begin", "tog_batch_stats_end", "tog_set_trajectory_costs", "tog_set_trajectory_goals",
     "tog_finished", "tog_get_slots", "tog_refill", "tog_refill_tables", "tog_solve_stream", "tog_solve_stream_tables",
-    "tog_rollout_plan", "tog_set_trajectory_obstacles", "tog_set_trajectory_bounds",
+    "tog_rollout_plan", "tog_set_trajectory_obstacles", "tog_set_trajectory_bounds", "tog_set_trajectory_weights",
 )
 KERNEL_JACOBIAN, KERNEL_BACKWARD, KERNEL_FORWARD, KERNEL_EXPANSION = 0, 1, 2, 3
 NKERNELS = 4

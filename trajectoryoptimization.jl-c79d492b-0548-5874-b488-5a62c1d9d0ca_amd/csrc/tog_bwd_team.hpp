@@ -445,7 +445,7 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
   double Qxc[n], Quuc[m], Qu[m], Qxs;
   const double xc = xg[c];
   const int diag_mode = P->diag_cost;
-  const CostView C_ = cost_at<n, m, PT>(P, TERM ? 0 : k, b);  // stage knot k's cost (a time-varying Objective)
+  const CostView C_ = cost_at<n, m, PT, PT>(P, TERM ? 0 : k, b);  // stage knot k's cost (a time-varying Objective)
   if (!TERM && diag_mode == 2) {
     // diagonal cost with +0.0 off-diagonals (host-checked): the per-lane constants are one
     // diagonal entry each, the rest literal zeros -- the same values the general path loads
@@ -489,15 +489,16 @@ __device__ __forceinline__ void team_expand(const DevProblem* P, const DevBuffer
     for (int i = 0; i < m; i++) Quuc[i] = SQRT ? C_.cR[i + m * cu] : C_.R[i + m * cu] * dt;
   } else {
     double a = 0.0;
+    const TermHView TH_ = termh_at<n, PT>(P, b);  // (trajectory b's Qf and factor: a per-lane load with the table)
     if (diag_mode) {
-      a = fma(P->Qf[c + n * c], xc, 0.0);
+      a = fma(TH_.Qf[c + n * c], xc, 0.0);
     } else {
 #pragma unroll
-      for (int j = 0; j < n; j++) a = fma(P->Qf[c + n * j], xg[j], a);
+      for (int j = 0; j < n; j++) a = fma(TH_.Qf[c + n * j], xg[j], a);
     }
     Qxs = a + term_at<n, PT>(P, b).qf[c];
 #pragma unroll
-    for (int i = 0; i < n; i++) Qxc[i] = SQRT ? P->cQf[i + n * c] : P->Qf[i + n * c];
+    for (int i = 0; i < n; i++) Qxc[i] = SQRT ? TH_.cQf[i + n * c] : TH_.Qf[i + n * c];
 #pragma unroll
     for (int i = 0; i < m; i++) {
       Qu[i] = 0.0;
@@ -738,7 +739,7 @@ __device__ __forceinline__ void quad_expand(const DevProblem* P, const DevBuffer
   constexpr int NXL = (n + TQ - 1) / TQ;  // Q.x entries of this lane: tl + TQ j
   double Qxs[NXL], Quuc[m], Qu[m];
   const int diag_mode = P->diag_cost;
-  const CostView C_ = cost_at<n, m, PT>(P, k, b);
+  const CostView C_ = cost_at<n, m, PT, PT>(P, k, b);
   if (diag_mode == 2) {
 #pragma unroll
     for (int j = 0; j < NXL; j++) {

@@ -112,6 +112,13 @@ struct DevProblem {
   // keeps in ConRow::b (no reader of a bound row uses b, c or r). bnd_ld = nb doubles per trajectory.
   const double* bnd;
   int bnd_ld, bnd_pad;
+  // Per-trajectory cost weights (tog_set_trajectory_weights; null: the Hessians above): per trajectory
+  // [Q; R; H; cQ; cR; Qf; cQf] (compact n, m, column-major; cQ, cR, cQf the square-root expansion's factors, as
+  // tog_create computes them for the shared cost), laid out (nh, B), hess_ld = nh = 4n² + 2m² + mn doubles per
+  // trajectory. A handle with the table carries the per-knot table kc too (cost_at looks for hess beside it), and
+  // diag_cost, sqrt_ok above are then the batch's: the minimum, and the AND, over the trajectories.
+  const double* hess;
+  int hess_ld, hess_pad;
 };
 
 // Read-only device tables seen through the constant address space. The row tables are read at the
@@ -1343,20 +1350,47 @@ __host__ __device__ constexpr int kc_stride_of() {
 // b: the trajectory (never a compacted launch's slot). With per-trajectory linear terms (DevProblem::lin) the
 // Hessians and factors are still the table's, and q, r, c are trajectory b's row, read through the global
 // address space (lane-indexed: vmcnt loads, not the flat loads of a generic pointer).
+// With per-trajectory weights (DevProblem::hess) Q, R, H, cQ, cR point into trajectory b's block instead, in every
+// variant: the lookup is not under PT, because the backward kernels ask for the Hessians alone with PT = false. It
+// sits after the early return, so a handle without a per-knot table never tests it. In the team kernels a wave
+// holds several trajectories, so reads through these pointers are per-lane loads.
 // PT = false compiles the per-trajectory tables out (cost_at, term_at, traj_row and the cost functions below):
 // the kernels on the shared objective's hot path are instantiated so and keep their code to the instruction,
 // and a handle with per-trajectory data launches their PT variants (DevBuffers::tv bit 1).
-template <int n, int m, bool PT = true>
+// offsets of the blocks in a trajectory's [Q; R; H; cQ; cR; Qf; cQf] (DevProblem::hess; tog_traj::HessLayout)
+template <int n, int m>
+struct HessOffsets {
+  static constexpr int R = n * n, H = R + m * m, cQ = H + m * n, cR = cQ + n * n, Qf = cR + m * m, cQf = Qf + n * n,
+                       nh = cQf + n * n;
+};
+// HS = false compiles the weight table out: the instantiations a weights handle can never launch (a handle with
+// the table sets DevBuffers::tv = 3, which selects the PT variants of the expansion kernels and the DC = 0
+// rollouts), so that the shared objective's kernels keep their code.
+template <int n, int m, bool PT = true, bool HS = true>
 __device__ __forceinline__ CostView cost_at(const DevProblem* P, int k, long long b) {
   if (!P->kc) return CostView{P->Q, P->R, P->H, P->q, P->r, P->cQ, P->cR, P->c};
   const double* t = P->kc + (size_t)k * kc_stride_of<n, m>();
   constexpr int oR = n * n, oH = oR + m * m, oq = oH + m * n, orr = oq + n, oc = orr + m, ocQ = oc + 1, ocR = ocQ + n * n;
+  CostView C{t, t + oR, t + oH, t + oq, t + orr, t + ocQ, t + ocR, 0.0};
+  if (HS && P->hess) {
+    constexpr HessOffsets<n, m> L{};
+    const double* w = (const double*)(as_global(P->hess) + (size_t)b * L.nh);
+    C.Q = w;
+    C.R = w + L.R;
+    C.H = w + L.H;
+    C.cQ = w + L.cQ;
+    C.cR = w + L.cR;
+  }
   if (PT && P->lin) {
     const size_t row = P->lin_per_knot ? (size_t)b * (P->N - 1) + k : (size_t)b;
     const gptr<double> l = as_global(P->lin) + row * (n + m + 1);
-    return CostView{t, t + oR, t + oH, (const double*)l, (const double*)(l + n), t + ocQ, t + ocR, l[n + m]};
+    C.q = (const double*)l;
+    C.r = (const double*)(l + n);
+    C.c = l[n + m];
+    return C;
   }
-  return CostView{t, t + oR, t + oH, t + oq, t + orr, t + ocQ, t + ocR, t[oc]};
+  C.c = t[oc];
+  return C;
 }
 // the terminal cost's linear and constant terms of trajectory b (DevProblem::term, else the shared qf, cf)
 struct TermView {
@@ -1370,6 +1404,21 @@ __device__ __forceinline__ TermView term_at(const DevProblem* P, long long b) {
     return TermView{(const double*)t, t[n]};
   }
   return TermView{P->qf, P->cf};
+}
+// the terminal cost's Hessian and its square-root factor as trajectory b sees them (DevProblem::hess, else the
+// shared Qf, cQf). PT = false compiles the table out, as in term_at. (Qf and cQf end the block, so their offsets
+// need the block's width alone: terminal_cost has no m.)
+struct TermHView {
+  const double *Qf, *cQf;
+};
+template <int n, bool PT = true>
+__device__ __forceinline__ TermHView termh_at(const DevProblem* P, long long b) {
+  if (PT && P->hess) {
+    const int nh = P->hess_ld;
+    const double* w = (const double*)(as_global(P->hess) + (size_t)b * nh);
+    return TermHView{w + (nh - 2 * n * n), w + (nh - n * n)};
+  }
+  return TermHView{P->Qf, P->cQf};
 }
 // A loaded constraint row as trajectory b sees it: a goal row takes its target from the goal table
 // (DevProblem::goal), a circle or sphere row its centre and radius from the obstacle table (DevProblem::obs, one
@@ -1405,7 +1454,7 @@ __device__ __forceinline__ ConRow traj_row(const DevProblem* P, long long b, Con
 template <int n, int m, int DC = 0, bool PT = (DC == 0)>
 __device__ __forceinline__ double stage_cost_dt(const DevProblem* P, long long b, int k, const double* x,
                                                 const double* u, double dt) {
-  const CostView C = cost_at<n, m, PT>(P, k, b);
+  const CostView C = cost_at<n, m, PT, PT>(P, k, b);  // (PT = false is DC = 1: never a weights handle's)
   double xQx = 0.0, uRu = 0.0, qx = 0.0, ru = 0.0, uHx = 0.0;
   if (DC == 1 || (DC == 0 && P->diag_cost)) {
 #pragma unroll
@@ -1447,15 +1496,16 @@ __device__ __forceinline__ double stage_cost(const DevProblem* P, long long b, i
 template <int n, int DC = 0, bool PT = (DC == 0)>
 __device__ __forceinline__ double terminal_cost(const DevProblem* P, long long b, const double* x) {
   const TermView T = term_at<n, PT>(P, b);
+  const double* Qf = termh_at<n, PT>(P, b).Qf;
   double xQx = 0.0, qx = 0.0;
   if (DC == 1 || (DC == 0 && P->diag_cost)) {
 #pragma unroll
-    for (int j = 0; j < n; j++) xQx = fma((0.5 * x[j]) * P->Qf[j + n * j], x[j], xQx);
+    for (int j = 0; j < n; j++) xQx = fma((0.5 * x[j]) * Qf[j + n * j], x[j], xQx);
   } else {
 #pragma unroll 1
     for (int j = 0; j < n; j++) {
       double t = 0.0;
-      for (int i = 0; i < n; i++) t = fma(0.5 * x[i], P->Qf[i + n * j], t);
+      for (int i = 0; i < n; i++) t = fma(0.5 * x[i], Qf[i + n * j], t);
       xQx = fma(t, x[j], xQx);
     }
   }

@@ -176,6 +176,44 @@ struct CostPlan {
   const double* cR(int k) const { return cQ(k) + n * n; }
 };
 
+// The square-root expansion's factors of one stage cost (src/objective.jl:70-94): cQ = chol(Q dt), cR = chol(R dt),
+// upper. 0 when both exist, else which of them is not positive definite: 1 Q dt (cR is then left as it was: R is not
+// factored after a failed Q), 2 R dt.
+inline int factor_stage(int n, int m, double dt, const double* Q, const double* R, double* cQ, double* cR) {
+  std::vector<double> Qdt((size_t)n * n), Rdt((size_t)m * m);
+  for (int i = 0; i < n * n; i++) Qdt[i] = Q[i] * dt;
+  for (int i = 0; i < m * m; i++) Rdt[i] = R[i] * dt;
+  if (!chol_upper(Qdt.data(), n, cQ)) return 1;
+  return chol_upper(Rdt.data(), m, cR) ? 0 : 2;
+}
+// The diagonal-cost class of one stage cost beside the terminal cost (CostPlan::diag_cost; a table's class, and a
+// batch of per-trajectory Hessians', is the minimum over its members): 0 dense; 1 diagonal Q, R, Qf and H = 0; 2 = 1
+// with every off-diagonal entry, H and (ok: when every factor exists) the factors' off-diagonals +0.0, and dt > 0.
+inline int cost_class(int n, int m, double dt, const double* Q, const double* R, const double* H, const double* Qf,
+                      const double* cQ, const double* cR, const double* cQf, bool ok) {
+  bool diag = true;
+  for (int j = 0; j < n; j++)
+    for (int i = 0; i < n; i++)
+      if (i != j && (Qf[i + n * j] != 0.0 || Q[i + n * j] != 0.0)) diag = false;
+  for (int j = 0; j < m; j++)
+    for (int i = 0; i < m; i++)
+      if (i != j && R[i + m * j] != 0.0) diag = false;
+  for (int i = 0; i < m * n; i++)
+    if (H[i] != 0.0) diag = false;
+  if (!diag) return 0;
+  auto offdiag_pz = [](const double* A, int kk) {
+    for (int j = 0; j < kk; j++)
+      for (int i = 0; i < kk; i++)
+        if (i != j && (A[i + kk * j] != 0.0 || std::signbit(A[i + kk * j]))) return false;
+    return true;
+  };
+  bool pz = dt > 0.0 && offdiag_pz(Qf, n) && (!ok || offdiag_pz(cQf, n)) && offdiag_pz(Q, n) && offdiag_pz(R, m);
+  if (pz && ok) pz = offdiag_pz(cQ, n) && offdiag_pz(cR, m);
+  for (int i = 0; pz && i < m * n; i++)
+    if (std::signbit(H[i])) pz = false;
+  return pz ? 2 : 1;
+}
+
 // stage_costs: the (nc_in, N - 1) table, or null for the shared Q, R, H, q, r, c
 inline CostPlan plan_costs(int n, int m, int N, double dt, const double* Q, const double* R, const double* H,
                            const double* q, const double* r, double c, const double* stage_costs,
@@ -205,42 +243,12 @@ inline CostPlan plan_costs(int n, int m, int N, double dt, const double* Q, cons
   auto kcR = [&](int k) { return kcQ(k) + n * n; };
   p.cQf.assign((size_t)n * n, 0.0);
   bool ok = chol_upper(Qf, n, p.cQf.data());
-  std::vector<double> Qdt((size_t)n * n), Rdt((size_t)m * m);
-  for (int k = 0; k < nk; k++) {
-    for (int i = 0; i < n * n; i++) Qdt[i] = p.Q(k)[i] * dt;
-    for (int i = 0; i < m * m; i++) Rdt[i] = p.R(k)[i] * dt;
-    ok = chol_upper(Qdt.data(), n, kcQ(k)) && chol_upper(Rdt.data(), m, kcR(k)) && ok;
-  }
+  for (int k = 0; k < nk; k++) ok = factor_stage(n, m, dt, p.Q(k), p.R(k), kcQ(k), kcR(k)) == 0 && ok;
   p.sqrt_ok = ok;
-  bool diag = true;
-  for (int j = 0; j < n; j++)
-    for (int i = 0; i < n; i++)
-      if (i != j && Qf[i + n * j] != 0.0) diag = false;
-  for (int k = 0; k < nk; k++) {
-    for (int j = 0; j < n; j++)
-      for (int i = 0; i < n; i++)
-        if (i != j && p.Q(k)[i + n * j] != 0.0) diag = false;
-    for (int j = 0; j < m; j++)
-      for (int i = 0; i < m; i++)
-        if (i != j && p.R(k)[i + m * j] != 0.0) diag = false;
-    for (int i = 0; i < m * n; i++)
-      if (p.H(k)[i] != 0.0) diag = false;
-  }
-  bool pz = diag && dt > 0.0;
-  auto offdiag_pz = [&](const double* A, int kk) {
-    for (int j = 0; j < kk; j++)
-      for (int i = 0; i < kk; i++)
-        if (i != j && (A[i + kk * j] != 0.0 || std::signbit(A[i + kk * j]))) return false;
-    return true;
-  };
-  if (pz) pz = offdiag_pz(Qf, n) && (!ok || offdiag_pz(p.cQf.data(), n));
-  for (int k = 0; pz && k < nk; k++) {
-    pz = offdiag_pz(p.Q(k), n) && offdiag_pz(p.R(k), m);
-    if (pz && ok) pz = offdiag_pz(p.cQ(k), n) && offdiag_pz(p.cR(k), m);
-    for (int i = 0; pz && i < m * n; i++)
-      if (std::signbit(p.H(k)[i])) pz = false;
-  }
-  p.diag_cost = diag ? (pz ? 2 : 1) : 0;
+  p.diag_cost = 2;
+  for (int k = 0; k < nk; k++)
+    p.diag_cost = std::min(p.diag_cost, cost_class(n, m, dt, p.Q(k), p.R(k), p.H(k), Qf, p.cQ(k), p.cR(k),
+                                                   p.cQf.data(), ok));
   return p;
 }
 

@@ -250,9 +250,10 @@ __device__ void expansion_gradient_entries(const DevProblem* __restrict__ P, con
       }
     } else {
       const TermView T_ = term_at<n>(P, b);
+      const double* Qf = termh_at<n>(P, b).Qf;
       for (int i = 0; i < n; i++) {
         double a = 0.0;
-        for (int j = 0; j < n; j++) a = fma(P->Qf[i + n * j], x[j], a);
+        for (int j = 0; j < n; j++) a = fma(Qf[i + n * j], x[j], a);
         q[i] = a + T_.qf[i];
       }
       if constexpr (MT) q[n - 1] = P->R_min_time * x[n - 1];
@@ -929,11 +930,12 @@ __device__ void bwd_expand(const DevProblem* __restrict__ P, const DevBuffers& B
       }
     }
   } else {
-    for (int e = lane; e < n * n; e += WAVE) sh.Qxx[e] = SQRT ? P->cQf[e] : P->Qf[e];
+    const TermHView TH_ = termh_at<n>(P, b);
+    for (int e = lane; e < n * n; e += WAVE) sh.Qxx[e] = SQRT ? TH_.cQf[e] : TH_.Qf[e];
     if (lane < n) {
       double a = 0.0;
 #pragma unroll
-      for (int j = 0; j < n; j++) a = fma(P->Qf[lane + n * j], sh.xk[j], a);
+      for (int j = 0; j < n; j++) a = fma(TH_.Qf[lane + n * j], sh.xk[j], a);
       sh.Qx[lane] = a + term_at<n>(P, b).qf[lane];
     }
     if constexpr (MT) {  // S.xx[end,end] = R_min_time, S.x[end] = R_min_time xN[end]
@@ -3483,11 +3485,12 @@ __global__ void __launch_bounds__(64) k_cost_expansion(const DevProblem* __restr
     for (int i = 0; i < m * m; i++) Quu[i] = C_.R[i] * dt;
     for (int i = 0; i < m * n; i++) Qux[i] = C_.H[i] * dt;
   } else {
-    for (int i = 0; i < n * n; i++) Qxx[i] = P->Qf[i];
+    const double* Qf = termh_at<n>(P, b).Qf;
+    for (int i = 0; i < n * n; i++) Qxx[i] = Qf[i];
     const TermView T_ = term_at<n>(P, b);
     for (int i = 0; i < n; i++) {
       double a = 0.0;
-      for (int j = 0; j < n; j++) a = fma(P->Qf[i + n * j], x[j], a);
+      for (int j = 0; j < n; j++) a = fma(Qf[i + n * j], x[j], a);
       Qx[i] = a + T_.qf[i];
     }
   }

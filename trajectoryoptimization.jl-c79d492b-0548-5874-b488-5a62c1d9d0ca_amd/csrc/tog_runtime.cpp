@@ -157,6 +157,10 @@ struct tog_handle {
   // ordinal of the descriptor's sets table whether its constraint is trimmed (nb = size)
   double* d_bnd = nullptr;
   std::vector<char> bnd_trimmed;
+  // per-trajectory cost weights (tog_set_trajectory_weights; DevProblem::hess): the device table (nh, B), the
+  // batch's sqrt_ok and diagonal-cost class while it is set, and the descriptor's, which clearing it restores
+  double* d_hess = nullptr;
+  int hess_sqrt_ok = 1, hess_diag = 0, sqrt_ok0 = 0, diag0 = 0;
   // Streamed solves (tog_finished / tog_get_slots / tog_refill / tog_solve_stream), allocated on first use and
   // freed in tog_destroy; everything is ordered on the handle's stream.
   // d_slot_job (B): the job a slot holds whose end has not been listed yet (-1: empty, or listed by
@@ -1007,6 +1011,8 @@ static int32_t fill_problem(tog_handle* h, const tog_problem_desc* d, const tog_
   P.sqrt_ok = cp.sqrt_ok ? 1 : 0;
   P.diag_cost = cp.diag_cost;
   h->buf.cost_diag = P.diag_cost;
+  h->sqrt_ok0 = P.sqrt_ok;
+  h->diag0 = P.diag_cost;
   if (opts->square_root && !cp.sqrt_ok)
     return fail(TOG_ERR_ARG, "cost Hessians must be PD for the sqrt backward pass (objective.jl:70-94)");
   // packed std AL expansion records: the Q.xx entries a stage row can change (row_grad's state indices)
@@ -1592,7 +1598,9 @@ static int32_t traj_apply(tog_handle* h) {
   // (the obstacle table needs no per-knot cost table: cost_at returns the shared cost without one, and the
   // backward kernels read no constraint row, so an obstacle-only handle sets variant bit 1 alone)
   // (nor does the bound table: it replaces a row's limit, which the same readers take through traj_row)
-  const bool cost = h->d_lin || h->d_term || h->d_goal, any = cost || h->d_obs || h->d_bnd;
+  // (the weight table counts as cost data: cost_at looks for it beside the per-knot table, and the backward
+  // kernels' per-knot-cost variants are the ones that read their Hessians through cost_at)
+  const bool cost = h->d_lin || h->d_term || h->d_goal || h->d_hess, any = cost || h->d_obs || h->d_bnd;
   if (cost && !h->kc0 && !h->d_kc_rep) {
     const std::vector<double> t = tog_traj::replicate_row(h->kc_row, h->N - 1);
     int32_t rc = dalloc(h, &h->d_kc_rep, t.size());
@@ -1608,6 +1616,12 @@ static int32_t traj_apply(tog_handle* h) {
   P.obs_ld = (int)tog_traj::obs_width((int)h->obs_kind.size());
   P.bnd = h->d_bnd;
   P.bnd_ld = (int)h->bnd_trimmed.size();
+  P.hess = h->d_hess;
+  P.hess_ld = (int)tog_traj::hess_width(h->n, h->m);
+  // (the cost's structure flags are the batch's while the table is set, the descriptor's again without it)
+  P.sqrt_ok = h->d_hess ? h->hess_sqrt_ok : h->sqrt_ok0;
+  P.diag_cost = h->d_hess ? h->hess_diag : h->diag0;
+  h->buf.cost_diag = P.diag_cost;
   h->buf.tv = ((h->tv0 || cost) ? 1 : 0) | (any ? 2 : 0);  // (bit 1: the per-trajectory kernel variants)
   HIPCHECK(hipStreamSynchronize(h->stream));
   HIPCHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
@@ -1733,6 +1747,45 @@ int32_t tog_set_trajectory_bounds(tog_handle* h, const double* bnd) {
   }
   HIPCHECK(hipSetDevice(h->device));
   const int32_t rc = traj_table(h, &h->d_bnd, bnd, bnd ? h->bnd_trimmed.size() * (size_t)h->B : 0);
+  const int32_t ra = traj_apply(h);
+  return rc ? rc : ra;
+}
+
+int32_t tog_set_trajectory_weights(tog_handle* h, const double* W) {
+  if (!h) return fail(TOG_ERR_ARG, "null handle");
+  if (is_multi(h)) {
+    const tog_handle* p0 = h->parts[0];
+    const size_t w = tog_traj::weights_width(p0->n, p0->m);
+    // (the whole table is checked before any part takes its slice: a refused table leaves every part's in place)
+    if (W && !p0->ops->slack && !p0->ops->min_time && !p0->kc0) {
+      long long Ball = 0;
+      for (const tog_handle* p : h->parts) Ball += p->B;
+      std::string err = tog_traj::weight_table_check(W, p0->n, p0->m, Ball);
+      if (err.empty() && p0->opts.square_root)
+        err = tog_traj::weight_pd_text(tog_traj::weight_plan(W, p0->n, p0->m, p0->hostP.dt, Ball));
+      if (!err.empty()) return fail(TOG_ERR_ARG, err);
+    }
+    return each_part(h, [&](tog_handle* p, size_t o) {
+      return tog_set_trajectory_weights(p, tog_traj::part_slice(W, o, w));
+    });
+  }
+  if (int32_t rr = traj_refuse(h, "tog_set_trajectory_weights")) return rr;
+  if (h->kc0) return fail(TOG_ERR_UNSUPPORTED, tog_traj::weights_varying_text());
+  tog_traj::WeightPlan wp;
+  if (W) {
+    std::string err = tog_traj::weight_table_check(W, h->n, h->m, h->B);
+    if (err.empty()) {
+      wp = tog_traj::weight_plan(W, h->n, h->m, h->hostP.dt, h->B);
+      if (h->opts.square_root) err = tog_traj::weight_pd_text(wp);
+    }
+    if (!err.empty()) return fail(TOG_ERR_ARG, err);  // (the table in place stays)
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  const int32_t rc = traj_table(h, &h->d_hess, W ? wp.image.data() : nullptr, wp.image.size());
+  if (!rc && W) {
+    h->hess_sqrt_ok = wp.sqrt_ok ? 1 : 0;
+    h->hess_diag = wp.diag_cost;
+  }
   const int32_t ra = traj_apply(h);
   return rc ? rc : ra;
 }
@@ -2087,6 +2140,8 @@ static int32_t obs_refuse(const tog_handle* h, const char* who) {
   if (h && !is_multi(h) && h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text(who));
   // likewise the bound table: a refilled slot would keep the last job's limits
   if (h && !is_multi(h) && h->d_bnd) return fail(TOG_ERR_UNSUPPORTED, tog_traj::bounds_set_text(who));
+  // and the weight table: a refilled slot would keep the last job's Hessians
+  if (h && !is_multi(h) && h->d_hess) return fail(TOG_ERR_UNSUPPORTED, tog_traj::weights_set_text(who));
   return TOG_OK;
 }
 
@@ -2569,6 +2624,7 @@ int32_t tog_solve_pn(tog_handle* h, const tog_pn_options* opts, double* out) {
                                      "shared objective and goal; clear them with NULL tables first)");
   if (h->d_obs) return fail(TOG_ERR_UNSUPPORTED, tog_traj::obstacles_set_text("tog_solve_pn"));
   if (h->d_bnd) return fail(TOG_ERR_UNSUPPORTED, tog_traj::bounds_set_text("tog_solve_pn"));
+  if (h->d_hess) return fail(TOG_ERR_UNSUPPORTED, tog_traj::weights_set_text("tog_solve_pn"));
   const bool optimal = opts->solve_type == 1;
   if (opts->n_steps < 0) return fail(TOG_ERR_ARG, "n_steps must be >= 0");
   if (!h->ops->pn) return fail(TOG_ERR_UNSUPPORTED, "projected Newton needs n + m <= 64 (a lane per variable of a knot)");

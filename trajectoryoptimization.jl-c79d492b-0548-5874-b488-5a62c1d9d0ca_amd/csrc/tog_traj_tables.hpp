@@ -3,10 +3,13 @@
 // to its parts, and the replace order of a device buffer (and of tog_history_enable's pair). Plain C++ with no device runtime in it, so that a
 // stand-alone program can run it under the host sanitizers (tests/c/traj_tables_host.cpp).
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "tog_host_plan.hpp"  // chol_upper, factor_stage, cost_class: the per-trajectory weights' factors and class
 
 namespace tog_traj {
 
@@ -183,6 +186,97 @@ inline std::string bounds_refuse_text() {
 inline std::string bounds_set_text(const char* who) {
   return std::string(who) + ": per-trajectory bounds are set (this call reads the descriptor's bounds; clear the "
                             "table with tog_set_trajectory_bounds(h, NULL) first)";
+}
+
+// ---- per-trajectory cost weights (tog_set_trajectory_weights): the Hessians Q, R, H and Qf of each trajectory.
+// The host array W is (nw, B): per trajectory [Q (n, n); R (m, m); H (m, n); Qf (n, n)], matrices column-major with
+// the compact n, m. The device table (DevProblem::hess) is (nh, B): per trajectory [Q; R; H; cQ; cR; Qf; cQf] with
+// cQ = chol(Q dt), cR = chol(R dt), cQf = chol(Qf), the factors tog_create computes for the shared cost
+// (tog_plan::factor_stage, chol_upper), so a member's block is bit for bit what a handle of its own would hold.
+inline size_t weights_width(int n, int m) { return 2 * (size_t)n * n + (size_t)m * m + (size_t)m * n; }
+inline size_t hess_width(int n, int m) { return 4 * (size_t)n * n + 2 * (size_t)m * m + (size_t)m * n; }
+// offsets of the blocks in a trajectory's device image
+struct HessLayout {
+  int R, H, cQ, cR, Qf, cQf, nh;
+  constexpr HessLayout(int n, int m)
+      : R(n * n), H(R + m * m), cQ(H + m * n), cR(cQ + n * n), Qf(cR + m * m), cQf(Qf + n * n), nh(cQf + n * n) {}
+};
+struct WeightPlan {
+  std::vector<double> image;  // (nh, B)
+  bool sqrt_ok = true;        // every trajectory's Hessians are PD (the AND over the batch)
+  int diag_cost = 2;          // the minimum over the batch of tog_plan::cost_class
+  // the first Hessian that is not positive definite, in the order tog_create factors them (Qf, Q, R): its
+  // trajectory (-1: none) and its name
+  long long bad_traj = -1;
+  const char* bad_mat = "";
+};
+// (nw, B) weights: empty when they can replace the shared Hessians, else why not: a NaN or an infinity, or a Q, R
+// or Qf that is not symmetric. The message names the trajectory and the matrix. (Positive definiteness, which a
+// square-root handle asks for, is weight_plan's finding: the factors are computed once, there.)
+inline std::string weight_table_check(const double* W, int n, int m, long long B) {
+  const size_t nw = weights_width(n, m);
+  const char* names[4] = {"Q", "R", "H", "Qf"};
+  const int dims[4][2] = {{n, n}, {m, m}, {m, n}, {n, n}};
+  for (long long b = 0; b < B; b++) {
+    const double* w = W + (size_t)b * nw;
+    const double* mat[4] = {w, w + n * n, w + n * n + m * m, w + n * n + m * m + m * n};
+    for (int k = 0; k < 4; k++) {
+      const int rows = dims[k][0], cols = dims[k][1];
+      for (int i = 0; i < rows * cols; i++)
+        if (mat[k][i] - mat[k][i] != 0.0)  // (NaN or infinite)
+          return "tog_set_trajectory_weights: trajectory " + std::to_string(b) + ": " + names[k] +
+                 " has a NaN or an infinite entry";
+      if (k == 2) continue;
+      for (int j = 0; j < cols; j++)
+        for (int i = 0; i < j; i++)
+          if (mat[k][i + rows * j] != mat[k][j + rows * i])
+            return "tog_set_trajectory_weights: trajectory " + std::to_string(b) + ": " + names[k] +
+                   " is not symmetric";
+    }
+  }
+  return std::string();
+}
+// the device table's host image with the batch's sqrt_ok and diagonal-cost class
+inline WeightPlan weight_plan(const double* W, int n, int m, double dt, long long B) {
+  const size_t nw = weights_width(n, m);
+  const HessLayout L(n, m);
+  WeightPlan p;
+  p.image.assign((size_t)L.nh * (size_t)B, 0.0);
+  for (long long b = 0; b < B; b++) {
+    const double* w = W + (size_t)b * nw;
+    const double *Q = w, *R = w + n * n, *H = R + m * m, *Qf = H + m * n;
+    double* o = p.image.data() + (size_t)b * L.nh;
+    memcpy(o, Q, sizeof(double) * n * n);
+    memcpy(o + L.R, R, sizeof(double) * m * m);
+    memcpy(o + L.H, H, sizeof(double) * m * n);
+    memcpy(o + L.Qf, Qf, sizeof(double) * n * n);
+    const bool okf = tog_plan::chol_upper(Qf, n, o + L.cQf);
+    const int st = tog_plan::factor_stage(n, m, dt, Q, R, o + L.cQ, o + L.cR);
+    const bool ok = okf && st == 0;
+    if (!ok && p.bad_traj < 0) {
+      p.bad_traj = b;
+      p.bad_mat = !okf ? "Qf" : (st == 1 ? "Q" : "R");
+    }
+    p.sqrt_ok = p.sqrt_ok && ok;
+    p.diag_cost = std::min(p.diag_cost, tog_plan::cost_class(n, m, dt, Q, R, H, Qf, o + L.cQ, o + L.cR, o + L.cQf, ok));
+  }
+  return p;
+}
+// a square-root handle's refusal of a plan whose Hessians are not all positive definite (empty: they are)
+inline std::string weight_pd_text(const WeightPlan& p) {
+  if (p.sqrt_ok) return std::string();
+  return "tog_set_trajectory_weights: trajectory " + std::to_string(p.bad_traj) + ": " + p.bad_mat +
+         " is not positive definite (the sqrt backward pass, objective.jl:70-94)";
+}
+// a handle whose descriptor came with a time-varying stage_costs table
+inline std::string weights_varying_text() {
+  return "tog_set_trajectory_weights: the problem has a time-varying stage_costs table (cost Hessians per "
+         "trajectory and per knot are not built)";
+}
+// the entry points whose kernels or staging read the descriptor's Hessians
+inline std::string weights_set_text(const char* who) {
+  return std::string(who) + ": per-trajectory cost weights are set (this call reads the descriptor's cost Hessians; "
+                            "clear the table with tog_set_trajectory_weights(h, NULL) first)";
 }
 
 // a host array's slice for the part of a multi-device handle that starts at trajectory `off` (the batch axis is

@@ -128,6 +128,11 @@ class BatchHandle:
             self.set_trajectory_bounds(bnd)
         elif getattr(self, "_traj_bounds", False):
             self.set_trajectory_bounds(None)
+        W = prob.trajectory_weights() if hasattr(prob, "trajectory_weights") else None
+        if W is not None:
+            self.set_trajectory_weights(W)
+        elif getattr(self, "_traj_weights", False):
+            self.set_trajectory_weights(None)
 
     def set_trajectory_costs(self, lin=None, term=None):
         """tog_set_trajectory_costs. lin: (B, n+m+1) rows [q; r; c], or (B, N-1, n+m+1) with a row per stage
@@ -187,6 +192,21 @@ class BatchHandle:
             raise ValueError(f"bnd must be ({self.B}, nb), got {bnd.shape}")
         abi.check(self.lib, self.lib.tog_set_trajectory_bounds(self.h, abi.as_dp(bnd)))
         self._traj_bounds = True
+
+    def set_trajectory_weights(self, W=None):
+        """tog_set_trajectory_weights. W: (B, nw) rows [Q; R; H; Qf], each matrix column-major with the compact
+        n and m, nw = 2n² + m² + mn (Problem.trajectory_weights); None: the descriptor's Hessians."""
+        if W is None:
+            abi.check(self.lib, self.lib.tog_set_trajectory_weights(self.h, C.cast(None, C.POINTER(C.c_double))))
+            self._traj_weights = False
+            return
+        n, m = self.n, self.m
+        nw = 2 * n * n + m * m + m * n
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.shape != (self.B, nw):
+            raise ValueError(f"W must be ({self.B}, {nw}), got {W.shape}")
+        abi.check(self.lib, self.lib.tog_set_trajectory_weights(self.h, abi.as_dp(W)))
+        self._traj_weights = True
 
     def download_state(self, prob):
         prob._X[...] = self.get(abi.FIELD_X)

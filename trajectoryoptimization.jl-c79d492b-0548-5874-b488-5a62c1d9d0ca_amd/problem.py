@@ -520,12 +520,19 @@ class BatchObjective(Objective):
     and differ in the linear and constant terms: what ``LQRObjective(Q, R, Qf, xf_b, N)`` gives a batch of goals,
     or a tracking cost a batch of references. As an Objective it is trajectory 0's (the problem descriptor's);
     ``self[b]`` is trajectory b's Objective, ``lin`` / ``term`` the tables of tog_set_trajectory_costs:
-    ``lin`` (B, n+m+1) rows [q; r; c] (``per_knot`` False) or (B, N-1, n+m+1), ``term`` (B, n+1) rows [qf; cf]."""
+    ``lin`` (B, n+m+1) rows [q; r; c] (``per_knot`` False) or (B, N-1, n+m+1), ``term`` (B, n+1) rows [qf; cf].
 
-    def __init__(self, objs):
+    ``hessians="trajectory"``: the members may also differ in their Hessians Q, R, H and Qf (a weight sweep); within
+    one member every stage knot then has the same Q, R, H. ``weights`` (B, nw) holds the rows [Q; R; H; Qf] of
+    tog_set_trajectory_weights, each matrix column-major with the compact n and m, nw = 2n² + m² + mn (None for a
+    batch of shared Hessians)."""
+
+    def __init__(self, objs, hessians="shared"):
         objs = list(objs)
         if not objs:
             raise ValueError("BatchObjective needs at least one Objective")
+        if hessians not in ("shared", "trajectory"):
+            raise ValueError(f'hessians must be "shared" or "trajectory", got {hessians!r}')
         o0 = objs[0]
         super().__init__(list(o0.cost))
         for b, o in enumerate(objs):
@@ -534,11 +541,22 @@ class BatchObjective(Objective):
             for k, (c, c0) in enumerate(zip(o.cost, o0.cost)):
                 if not isinstance(c, QuadraticCost):
                     raise ValueError(f"trajectory {b}, knot {k}: a BatchObjective holds QuadraticCosts")
+                if hessians == "trajectory":
+                    if c.sizes() != c0.sizes():
+                        raise ValueError(f"trajectory {b}, knot {k}: cost sizes {c.sizes()} != {c0.sizes()}")
+                    if 0 < k < len(o) - 1:  # (the terminal cost's Q is Qf, its R and H are empty)
+                        for f in ("Q", "R", "H"):
+                            if not np.array_equal(getattr(c, f), getattr(o.cost[0], f)):
+                                raise ValueError(f"trajectory {b}, knot {k}: Hessian {f} differs from knot 0's "
+                                                 "(per-trajectory Hessians are one set per trajectory; a "
+                                                 "time-varying objective keeps the batch's)")
+                    continue
                 for f in ("Q", "R", "H"):
                     if not np.array_equal(getattr(c, f), getattr(c0, f)):
                         raise ValueError(f"trajectory {b}, knot {k}: Hessian {f} differs from trajectory 0's "
                                          "(a batch shares its Hessians; only q, r, c may differ)")
         self.objs = objs
+        self.hessians = hessians
         self.per_knot = any(o.varying for o in objs)
         n = o0.stage.Q.shape[0]
         m = max(c.r.size for o in objs for c in o.cost[:-1])
@@ -553,6 +571,17 @@ class BatchObjective(Objective):
             self.lin = np.stack([row(o.stage) for o in objs])
         self.term = np.stack([np.concatenate([o.terminal.q, [o.terminal.c]]) for o in objs])
         assert self.term.shape == (len(objs), n + 1)
+        self.weights = None
+        if hessians == "trajectory":
+            def wrow(o):
+                c = o.stage
+                R = c.R if c.R.size else np.zeros((m, m))
+                H = c.H if c.H.size else np.zeros((m, n))
+                return np.concatenate([c.Q.ravel(order="F"), R.ravel(order="F"), H.ravel(order="F"),
+                                       o.terminal.Q.ravel(order="F")])
+
+            self.weights = np.stack([wrow(o) for o in objs])
+            assert self.weights.shape == (len(objs), 2 * n * n + m * m + m * n)
 
     @property
     def B(self):
@@ -564,11 +593,27 @@ class BatchObjective(Objective):
 
 def LQRObjectiveBatch(Q, R, Qf, XF, N) -> BatchObjective:
     """``LQRObjective(Q, R, Qf, XF[b], N)`` for every row of XF (B, n), as one BatchObjective: each member is built
-    by LQRObjective itself, so a trajectory's q, c, qf, cf are bit for bit a single-goal problem's."""
+    by LQRObjective itself, so a trajectory's q, c, qf, cf are bit for bit a single-goal problem's. Any of Q, R, Qf
+    may be (B, n, n) / (B, m, m), a matrix per trajectory (a 2-D one is shared); the result is then a
+    ``hessians="trajectory"`` batch, member b being ``LQRObjective(Q[b], R[b], Qf[b], XF[b], N)``."""
     XF = np.asarray(XF, dtype=np.float64)
     if XF.ndim != 2:
         raise ValueError("XF must be (B, n)")
-    return BatchObjective([LQRObjective(Q, R, Qf, xf, N) for xf in XF])
+    B = XF.shape[0]
+    mats = {"Q": np.asarray(Q, dtype=np.float64), "R": np.asarray(R, dtype=np.float64),
+            "Qf": np.asarray(Qf, dtype=np.float64)}
+    for name, a in mats.items():
+        if a.ndim == 3 and a.shape[0] != B:
+            raise ValueError(f"{name} holds the matrices of {a.shape[0]} trajectories, XF the goals of {B}")
+        if a.ndim not in (2, 3):
+            raise ValueError(f"{name} must be a matrix or (B, ., .), got shape {a.shape}")
+    per_traj = any(a.ndim == 3 for a in mats.values())
+
+    def at(a, b):
+        return a[b] if a.ndim == 3 else a
+
+    return BatchObjective([LQRObjective(at(mats["Q"], b), at(mats["R"], b), at(mats["Qf"], b), XF[b], N)
+                           for b in range(B)], hessians="trajectory" if per_traj else "shared")
 
 
 # ----------------------------------------------------------------------------- constraints
@@ -1132,6 +1177,14 @@ class Problem:
     def has_trajectory_bounds(self) -> bool:
         return any(isinstance(c, BoundConstraint) and c.batched for cs in self.constraints.C for c in cs)
 
+    def trajectory_weights(self):
+        """(B, nw) rows [Q; R; H; Qf] of a ``hessians="trajectory"`` BatchObjective (tog_set_trajectory_weights), or
+        None."""
+        return getattr(self.obj, "weights", None)
+
+    def has_trajectory_weights(self) -> bool:
+        return self.trajectory_weights() is not None
+
     def has_trajectory_data(self) -> bool:
         return (isinstance(self.obj, BatchObjective) or self.trajectory_goals() is not None
                 or self.has_trajectory_obstacles() or self.has_trajectory_bounds())
@@ -1183,7 +1236,7 @@ class Problem:
             raise IndexError(f"trajectories [{lo}, {hi}) of {self.B}")
         p = _copy.copy(self)
         if isinstance(self.obj, BatchObjective):
-            p.obj = BatchObjective(self.obj.objs[lo:hi])
+            p.obj = BatchObjective(self.obj.objs[lo:hi], hessians=self.obj.hessians)
         p.constraints = _copy_constraints(self.constraints)
         memo = {}
         for k in range(self.N):

@@ -428,6 +428,35 @@ def config_quadrotor_bounds(B=8192, offset=0):
     return out, opts
 
 
+QUAD_WEIGHTS_LOG10 = 0.5  # config_quadrotor_weights: each diagonal weight is scaled by 10^U(-0.5, 0.5)
+QUAD_WEIGHTS_SEED = 6100  # and trajectory b's factors are drawn from default_rng(QUAD_WEIGHTS_SEED + b)
+
+
+def config_quadrotor_weights(B=8192, N=101, offset=0):
+    """Config 3 as a weight sweep (tog_set_trajectory_weights): each trajectory has its own positive diagonal
+    scaling of Q, R and Qf. Every diagonal entry of the three is multiplied by its own factor 10^U(-0.5, 0.5), a
+    range of one decade around config 3's Q = R = 1e-2 I, Qf = 1000 I (seed 6100+b, drawn in the order Q (13), R (4),
+    Qf (13)). x0, U0 (their first N - 1 knots) and the options are config 3's; N other than 101 keeps the final
+    time of 5 s (dt = 5 / (N - 1)). In the oracle each of the first 8 trajectories ends AL_CONVERGED, at N = 101
+    and at N = 21, on a solution that differs from the one config 3's own weights give it;
+    tests/test_trajectory_weights.py holds them to it."""
+    prob, opts = config_quadrotor(B=B, offset=offset)
+    n, m = 13, 4
+    st, term = prob.obj.stage, prob.obj.terminal
+    S = 10.0 ** _per_traj_rng(QUAD_WEIGHTS_SEED + offset, B, lambda r: r.uniform(-QUAD_WEIGHTS_LOG10, QUAD_WEIGHTS_LOG10, 2 * n + m))
+    eye_n, eye_m = np.eye(n), np.eye(m)
+    Q = S[:, None, 0:n] * eye_n * np.diag(st.Q)
+    R = S[:, None, n:n + m] * eye_m * np.diag(st.R)
+    Qf = S[:, None, n + m:] * eye_n * np.diag(term.Q)
+    obj = LQRObjectiveBatch(Q, R, Qf, np.tile(prob.xf, (B, 1)), N)
+    cons = Constraints(N)
+    for k in range(N):
+        cons[k] = prob.constraints[k if k < N - 1 else prob.N - 1]
+    out = Problem(prob.model, obj, constraints=cons, x0=prob.x0, xf=prob.xf, N=N, dt=prob.dt * (prob.N - 1) / (N - 1))
+    out._U[...] = prob._U[:, :N - 1]
+    return out, opts
+
+
 def config_kuka(B=4096, offset=0):
     """Config 5: Kuka iiwa (n=14, m=7, N=51), AL-iLQR with the terminal goal and the notebook's options;
     x0[1:7] ~ U(-0.2, 0.2) (seed 4000+b), U0 = the hold trajectory at x0 (the notebook's own

@@ -435,7 +435,7 @@ def _raise_pn_errors(flags, solver):
 
 def _refuse_trajectory_data(prob, who):
     """ALTRO's descriptor-level transforms and projected Newton read the shared objective and goal: a problem
-    with a BatchObjective, per-trajectory goals, obstacles or bounds is refused before anything reaches the
+    with a BatchObjective (its linear terms or its Hessians), per-trajectory goals, obstacles or bounds is refused before anything reaches the
     device."""
     if getattr(prob, "has_trajectory_data", None) and prob.has_trajectory_data():
         raise ValueError(f"{who}: the problem has per-trajectory costs, goals, obstacles or bounds (BatchObjective, "
@@ -633,6 +633,10 @@ def solve_stream(prob, opts, slots: int | None = None, device: int = 0, max_step
         raise ValueError("solve_stream: the problem has per-trajectory bounds (BoundConstraint limits (B, n) / "
                          "(B, m)); a refilled slot would keep the last job's limits. Solve it in batches with "
                          "solve_b")
+    if prob.has_trajectory_weights():
+        raise ValueError("solve_stream: the problem has per-trajectory cost weights (BatchObjective "
+                         'hessians="trajectory"); a refilled slot would keep the last job\'s Hessians. Solve it in '
+                         "batches with solve_b")
     if isinstance(opts, AugmentedLagrangianSolverOptions) and not prob.is_constrained():
         opts = opts.opts_uncon  # as solve_b (augmented_lagrangian_methods.jl:33-36)
     J = prob.B
